@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- decode tokens/s of the QServe W4A8KV4 hot path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One "step" = one decode step (one new token for each of the 16 sequences) of Llama-3-8B
@@ -15,7 +15,9 @@ one fp16 sum all-reduce over RCCL / xGMI after o_proj and after down_proj INSIDE
 max-over-ranks time, `tensor_parallel.all_reduce_us` reported.  Its N = 1 point is `llama2_70b_tp1` of the one-GPU line (or
 `bench.py --model llama2-70b`).  `--replicas` keeps the old N > 1 mode: N independent copies of configs[1], no collective.
 
-Rank 0 prints ONE JSON line.  Extra objects:
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints the line (`ms_per_step` = wall
+clock of the K timed steps / K).  --dump-outputs DIR then also writes what the last timed step computed (dump_outputs()).
+With --full the line also carries the extra objects below (and, with N > 1, the stand-alone collective timings):
   roofline      dominant kernel = the gate_up W4A8 GEMV (N=28672, K=4096, M=16) in the form the step runs
                 it (fusion level 3: with the silu_and_mul epilogue): algorithmic bytes (packed weights +
                 activations + output) / average duration measured with HIP events on the launch stream,
@@ -608,6 +610,30 @@ def cpu_baseline(cfg, batch):
                           batch, M, cores, reps, dt * reps, cfg.layers)}
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(runner, out_dir):
+    """What the timed decode step hands back, from its last step: `tokens` (the next token id of every sequence, float64 so
+    the ids are exact), `hidden` (the final-norm output lm_head reads, float32 [B, hidden]) and `residual` (the residual
+    stream after the last layer, float32 [B, hidden]).  Seeded inputs: the same arguments give the same inputs on every run.
+    Above DUMP_MAX_BYTES in all, `hidden` / `residual` keep a fixed, seeded sample of rows (`rows` lists them)."""
+    import numpy as np
+    B, H = runner.normed.shape
+    out = {"tokens": runner.tokens.detach().cpu().numpy().astype(np.float64)}
+    keep = min(B, max(1, (DUMP_MAX_BYTES - 16 * B) // (2 * 4 * H)))
+    rows = None if keep == B else np.sort(np.random.default_rng(0).choice(B, size=keep, replace=False))
+    for name, t in (("hidden", runner.normed), ("residual", runner.x)):
+        a = t.detach().float().cpu().numpy()
+        out[name] = a if rows is None else a[rows]
+    if rows is not None:
+        out["rows"] = rows.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+    return sorted(out)
+
+
 def _free_port():
     import socket
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as sk:
@@ -689,8 +715,13 @@ def main():
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--no-fused", action="store_true", help="reference call sequence (no fused extension kernels)")
     ap.add_argument("--fused-level", type=int, default=3, help="0 reference sequence, 1 fused add+norm / silu+quant, 2 + deferred split-K epilogue, 3 + no quantiser row kernels (SiLU in the gate_up epilogue, o / down quantise on the fly))")
-    ap.add_argument("--no-lserve", action="store_true", help="skip the configs[3] (LServe, 256K context) leg")
-    ap.add_argument("--no-extras", action="store_true", help="skip roofline / cpu_baseline / gemm_4096 legs")
+    ap.add_argument("--full", action="store_true", help="after the headline, also run every secondary leg (roofline, "
+                    "w4a8_gemm_4096, mid_m, protocol, drop_in, configs[2], LServe, Llama-2-70B, cpu_baseline) and, with N > 1, "
+                    "the stand-alone collective timings; off: set up, warm up, time the steps, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last step "
+                    "computed as DIR/<name>.npy (float32 / float64, at most 64 MB in all; see dump_outputs)")
+    ap.add_argument("--no-lserve", action="store_true", help="with --full: skip the configs[3] (LServe, 256K context) leg")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the secondary legs (roofline, cpu_baseline, ...)")
     ap.add_argument("--tp-comm", choices=["rccl", "peer"], default="rccl",
                     help="with --tp: the two all-reduces per layer on torch.distributed / RCCL (default) or on the library's own "
                          "peer-mapped collective folded into the add + norm kernel (omniserve_amd/tp.py: PeerComm; validated with "
@@ -698,6 +729,8 @@ def main():
     ap.add_argument("--tp", action="store_true", help="(default with N > 1; kept for older command lines) shard ONE model over "
                     "the N GPUs: Megatron TP, fp16 sum all-reduce after o_proj / down_proj inside the step; strong scaling")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # no launcher around us: become one.  One process per GPU under torch.distributed.run, same arguments.
@@ -764,6 +797,8 @@ def main():
     torch.cuda.synchronize()
     if not torch.isfinite(runner.x.float()).all():
         raise SystemExit("non-finite activations in the decode step")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(runner, args.dump_outputs)
 
     ar = None
     if dist is not None:
@@ -774,6 +809,7 @@ def main():
               "graph_capture_fell_back_to_eager": runner.graph_error if runner.graph_error else False}
     if tp:
         ar.update({"payload_bytes": args.batch * cfg.hidden * 2, "calls_per_step": 2 * cfg.layers, "step_collective": args.tp_comm})
+    if tp and args.full:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         buf = torch.zeros((args.batch, cfg.hidden), dtype=torch.float16, device=device)
         nbytes = buf.numel() * 2
@@ -836,7 +872,7 @@ def main():
         except Exception as exc:   # noqa: BLE001
             result[name] = {"error": "%s: %s" % (type(exc).__name__, exc)}
 
-    if rank == 0 and not args.no_extras and (world == 1 or not tp):
+    if rank == 0 and args.full and not args.no_extras and (world == 1 or not tp):
         leg("roofline", lambda: roofline_gate_up(runner, elapsed / args.steps * 1e3))
         prefetch_mb = runner.prefetch_bytes / float(1 << 20)
         result["config"]["l2_prefetch_mib_per_row_kernel"] = prefetch_mb

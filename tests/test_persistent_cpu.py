@@ -1,6 +1,11 @@
 """omniserve_amd.persistent.PersistentActivationBuffer hands out what the reference's layers expect to find in
-`input_metadata.activation_buffer`: pinned against the reference's own class where /root/reference is present
-(omniserve/utils/input_metadata.py:18-112), and self-consistent everywhere."""
+`input_metadata.activation_buffer`: pinned against the reference's own class (omniserve/utils/input_metadata.py:18-112) through
+tests/golden/activation_buffer.json (names, shapes, dtypes, strides, aliasing, sizes of its views), which is re-derived from
+that class and must match where the reference tree is present; self-consistent everywhere.
+
+    python -m tests.test_persistent_cpu      # rewrites tests/golden/activation_buffer.json (needs the reference tree)"""
+import json
+import os
 import types
 
 import pytest
@@ -37,9 +42,22 @@ def test_views_are_slices_of_one_allocation_and_alias_like_upstream():
         pab.view_for(0)
 
 
-@pytest.mark.skipif(not refstack.reference_available(), reason="/root/reference is not on this machine")
-@pytest.mark.parametrize("T", [1, 7, 128, 300])
-def test_view_matches_the_reference_activation_buffer(T):
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "activation_buffer.json")
+TOKENS = [1, 7, 128, 300]
+# aliasing relations inside each object (offset from the fp16 / int8 base allocations)
+ALIASES = (("act_buffer", ["qkv_proj_act_buffer", "out_down_proj_act_buffer"]),
+           ("quantized_act_buffer", ["quantized_hidden_states_buffer"]))
+SIZES = ("batched_seq_len", "hidden_size", "intermediate_size", "q_size", "kv_size", "chunk_prefill_size")
+
+
+def _describe(buf):
+    ts = _tensors(buf)
+    return {"tensors": {n: [list(t.shape), str(t.dtype), list(t.stride())] for n, t in sorted(ts.items())},
+            "alias_offsets": {n: ts[n].data_ptr() - ts[base].data_ptr() for base, names in ALIASES for n in names},
+            "sizes": {n: getattr(buf, n) for n in SIZES}}
+
+
+def _reference_view(T):
     with refstack.reference_over_mirror():
         from omniserve.utils.input_metadata import ActivationBuffer
 
@@ -53,16 +71,28 @@ def test_view_matches_the_reference_activation_buffer(T):
         model.config = types.SimpleNamespace(intermediate_size=INTER, hidden_size=HID)
         ref = ActivationBuffer(model, T)
         ref.allocate_activation_buffer()
-    ours = PersistentActivationBuffer(HID, INTER, QS, KVS, max_tokens=300, chunk_prefill_size=128, device="cpu").view_for(T)
-    rt, ot = _tensors(ref), _tensors(ours)
-    assert set(rt) == set(ot), (sorted(rt), sorted(ot))
-    for name, t in rt.items():
-        o = ot[name]
-        assert tuple(o.shape) == tuple(t.shape) and o.dtype == t.dtype and o.stride() == t.stride(), name
-    # aliasing relations inside each object are the same (offset from the fp16 / int8 base allocations)
-    for base, names in (("act_buffer", ["qkv_proj_act_buffer", "out_down_proj_act_buffer"]),
-                        ("quantized_act_buffer", ["quantized_hidden_states_buffer"])):
-        for n in names:
-            assert rt[n].data_ptr() - rt[base].data_ptr() == ot[n].data_ptr() - ot[base].data_ptr() == 0, n
-    for name in ("batched_seq_len", "hidden_size", "intermediate_size", "q_size", "kv_size", "chunk_prefill_size"):
-        assert getattr(ref, name) == getattr(ours, name), name
+    return _describe(ref)
+
+
+@pytest.mark.parametrize("T", TOKENS)
+def test_view_matches_the_reference_activation_buffer(T):
+    with open(GOLDEN) as f:
+        want = json.load(f)[str(T)]
+    if refstack.reference_available():
+        assert _reference_view(T) == want, "tests/golden/activation_buffer.json is stale: python -m tests.test_persistent_cpu"
+    assert all(off == 0 for off in want["alias_offsets"].values()), want["alias_offsets"]
+    ours = _describe(PersistentActivationBuffer(HID, INTER, QS, KVS, max_tokens=300, chunk_prefill_size=128,
+                                                device="cpu").view_for(T))
+    assert set(ours["tensors"]) == set(want["tensors"]), (sorted(want["tensors"]), sorted(ours["tensors"]))
+    for name, t in want["tensors"].items():
+        assert ours["tensors"][name] == t, name
+    assert ours["alias_offsets"] == want["alias_offsets"]
+    for name in SIZES:
+        assert ours["sizes"][name] == want["sizes"][name], name
+
+
+if __name__ == "__main__":
+    with open(GOLDEN, "w") as f:
+        json.dump({str(T): _reference_view(T) for T in TOKENS}, f, indent=1, sort_keys=True)
+        f.write("\n")
+    print("wrote", GOLDEN)

@@ -1,12 +1,16 @@
-"""Drop-in check against the REFERENCE's own source (build container only; skipped where /root/reference is absent):
-every call the reference's Python makes into `omniserve_backend.*`, `block_sparse_attn` and `flash_attn` is found with
-`ast`, and its positional / keyword arguments must bind to the function of the same name in this repo's mirror
-(omniserve_amd/backend/*.py through the omniserve_backend alias package).  The reference passes everything
-positionally (w4a8_linear.py:112-135, decoding_attention.py:162-179,326-353,389-421, ctx_update_kv.py:109-135,
-layernorm.py:86-101), so a mirror with a wrong arity or a renamed function fails here without a GPU."""
+"""Drop-in check against the REFERENCE's own source: every call the reference's Python makes into `omniserve_backend.*`,
+`block_sparse_attn` and `flash_attn` is found with `ast`, and its positional / keyword arguments must bind to the function of
+the same name in this repo's mirror (omniserve_amd/backend/*.py through the omniserve_backend alias package).  The reference
+passes everything positionally (w4a8_linear.py:112-135, decoding_attention.py:162-179,326-353,389-421, ctx_update_kv.py:109-135,
+layernorm.py:86-101), so a mirror with a wrong arity or a renamed function fails here without a GPU.  The scan's result
+(file, line, module, function, positional count, keyword names of each call) is stored in tests/golden/reference_callsites.json;
+where the reference tree is present the scan is re-run and must match it.
+
+    python -m tests.test_reference_callsites_cpu      # rewrites tests/golden/reference_callsites.json (needs the reference tree)"""
 import ast
 import importlib
 import inspect
+import json
 import os
 
 import pytest
@@ -71,9 +75,19 @@ def _call_sites():
     return sites
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="/root/reference is not on this machine")
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_callsites.json")
+
+
+def _stored_sites():
+    with open(GOLDEN) as f:
+        return [(s[0], s[1], s[2], s[3], s[4], tuple(s[5])) for s in json.load(f)]
+
+
 def test_every_reference_call_site_binds_to_the_mirror():
-    sites = _call_sites()
+    sites = _stored_sites()
+    if os.path.isdir(REF):
+        assert sorted(_call_sites()) == sorted(sites), ("tests/golden/reference_callsites.json is stale: "
+                                                       "python -m tests.test_reference_callsites_cpu")
     modules = {s[2] for s in sites}
     # the hot path's modules must all be reached by at least one call site (guards the scanner itself)
     for must in ("omniserve_backend.qgemm_w4a8_per_chn", "omniserve_backend.qgemm_w4a8_per_group",
@@ -104,3 +118,9 @@ def test_every_reference_call_site_binds_to_the_mirror():
             problems.append("%s:%d %s.%s(%d positional, keywords %s) does not bind: %s" % (
                 path, line, mod, fn, nargs, list(kwnames), e))
     assert not problems, "\n".join(problems)
+
+
+if __name__ == "__main__":
+    with open(GOLDEN, "w") as f:
+        f.write("[\n%s\n]\n" % ",\n".join(json.dumps(list(s[:5]) + [list(s[5])]) for s in sorted(_call_sites())))
+    print("wrote", GOLDEN)
