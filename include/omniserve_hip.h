@@ -374,7 +374,10 @@ size_t omni_kv4_decode_workspace_bytes(int batch, int num_heads, int head_dim, i
  * INCLUDING the current token (tlen = len-1 is the RoPE position and the append slot).
  * Applies neox RoPE to q and k, quantises + appends k,v of the current token to the pages,
  * attends over the cached history (fp16 dequant) plus the un-quantised current token, writes
- * out fp16 [B,Hq,Dh] contiguous.  max_context bounds lengths[] (sizes the KV split). */
+ * out fp16 [B,Hq,Dh] contiguous.  max_context bounds lengths[] (sizes the KV split).
+ * Heads: num_heads % num_kv_heads == 0, any ratio (7 = Yi-34B, 3, 5, 6, 10, ...): a workgroup serves a tile of up to 4 or 8
+ * q heads of one kv head, and a ratio that is no whole number of tiles ends in a ragged tile whose padded head slots read
+ * no q and store nothing.  The same holds for the partial / fine-grained / per-tensor KV8 decode entries below. */
 int omni_kv4_decode_attention(void* out_f16, const void* q_f16, const void* k_f16, const void* v_f16,
                               int64_t q_stride, int64_t kv_stride, const void* kv_pointers_i64,
                               const void* lengths_i32, int batch, int max_blocks, int num_heads,
@@ -432,7 +435,8 @@ int omni_kv_min_max_pool(const void* k_f16, const void* kv_pointers_i64, const v
 /* Replaces omniserve_backend.fused_attention_selector.single_query_page_selector
  *   (sparse_utils/KVPageSelector/fused_kv_page_selector.cpp:262-334): for retrieval heads,
  *   out[b,h,c] = fp16( sum_d max(q_d*kmax[c,d], q_d*kmin[c,d]) ) over the sub-chunks c of the history
- *   (q rotated at position lengths[b]-1); out fp16 [B,Hq,padded_sub_chunks] must be zero filled. */
+ *   (q rotated at position lengths[b]-1); out fp16 [B,Hq,padded_sub_chunks] must be zero filled.
+ *   num_heads % num_kv_heads == 0, any ratio. */
 int omni_kv_page_selector(void* out_f16, const void* q_f16, int64_t q_stride, const void* kv_pointers_i64,
                           const void* retrieval_head_flags_i32, const void* head_rank_table_i32,
                           const void* lengths_i32, int batch, int max_blocks, int num_heads, int num_kv_heads,

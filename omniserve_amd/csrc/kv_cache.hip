@@ -302,6 +302,7 @@ struct DecodeArgs {
   const int64_t* kv_pointers;  // [B,2,max_blocks]
   const int* lengths;
   int batch, max_blocks, num_heads, num_kv_heads;
+  int group;               // q heads per kv head (any value >= 1: the last head tile of a kv head may be ragged, see the kernel)
   KvLayout lay;
   int nsplit;              // KV splits (grid.x)
   int split_tokens;        // max tokens per split (multiple of 16)
@@ -413,7 +414,7 @@ __global__ __launch_bounds__(DEC_THREADS, OMNI_FLASH_MIN_BLOCKS) void kv4_decode
   // they are first used -- three dependent kernarg round trips (rider test, geometry, pointers) in front of the first vector
   // load of a kernel that is a chain of memory round trips (ISA of round 4, profiles/r04_e).
   asm volatile("" ::"s"(p.out), "s"(p.q), "s"(p.k), "s"(p.v), "s"(p.q_stride), "s"(p.kv_stride), "s"(p.kv_pointers), "s"(p.lengths),
-               "s"(p.batch), "s"(p.max_blocks), "s"(p.num_heads), "s"(p.num_kv_heads), "s"(p.lay.tpb), "s"(p.lay.tpb_log2),
+               "s"(p.batch), "s"(p.max_blocks), "s"(p.num_heads), "s"(p.num_kv_heads), "s"(p.group), "s"(p.lay.tpb), "s"(p.lay.tpb_log2),
                "s"(p.lay.num_kv_heads), "s"(p.lay.bytes_per_seq), "s"(p.nsplit), "s"(p.split_tokens), "s"(p.rope), "s"(p.rope_max_pos),
                "s"(p.part_ml), "s"(p.part_o), "s"(p.qs.slab), "s"(p.tickets), "s"(p.amax));
   if constexpr (LASTM) {
@@ -443,11 +444,17 @@ __global__ __launch_bounds__(DEC_THREADS, OMNI_FLASH_MIN_BLOCKS) void kv4_decode
 
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int split = blockIdx.x;
-  const int group = p.num_heads / p.num_kv_heads;
-  const int qg = group / G;
+  // Head tiles: a kv head's `group` q heads are served G at a time by ceil(group / G) workgroups.  The LAST tile is ragged when
+  // G does not divide the group (Yi-34B: 7 q heads per kv head): it has `valid` < G real heads.  A padded head slot gets a
+  // zero q row (nothing is read for it), runs through the sweep like a real head (zero scores: finite, no divergent path) and
+  // stores nothing -- no output row, no partials, no row maximum.  Head columns never mix in the MFMAs or the softmax, so
+  // the real heads' bits do not depend on what sits beside them.
+  const int group = p.group;
+  const int qg = (group + G - 1) / G;
   const int hk = blockIdx.y / qg;
   const int sub = blockIdx.y % qg;
   const int hq0 = hk * group + sub * G;
+  const int valid = min(G, group - sub * G);       // real heads of this tile (workgroup-uniform)
   const int b = blockIdx.z;
   OMNI_CLK(16);
   const KvLayout lay = p.lay;
@@ -523,10 +530,12 @@ __global__ __launch_bounds__(DEC_THREADS, OMNI_FLASH_MIN_BLOCKS) void kv4_decode
     for (int j = 0; j < QIT; ++j) {
       const int idx = tid + j * DEC_THREADS;
       const int h = idx >> 6, i = idx & 63;
-      const half_t* src = h < G ? p.q + (size_t)b * p.q_stride + (size_t)(hq0 + h) * DH
-                                : p.k + (size_t)b * p.kv_stride + (size_t)hk * DH;   // h > G (idle slots): k again
-      qa[j] = src[i];
-      qbv[j] = src[i + 64];
+      const half_t* src = h < valid ? p.q + (size_t)b * p.q_stride + (size_t)(hq0 + h) * DH
+                                    : p.k + (size_t)b * p.kv_stride + (size_t)hk * DH;   // h > G (idle slots): k again
+      const bool pad = h >= valid && h < G;      // padded head slot: reads k like an idle slot, keeps zero
+      const half_t x0 = src[i], x1 = src[i + 64];
+      qa[j] = pad ? (half_t)0.0f : x0;
+      qbv[j] = pad ? (half_t)0.0f : x1;
     }
     if (tid < DH) vcur_r = p.v[(size_t)b * p.kv_stride + (size_t)hk * DH + tid];
   } else {
@@ -541,7 +550,7 @@ __global__ __launch_bounds__(DEC_THREADS, OMNI_FLASH_MIN_BLOCKS) void kv4_decode
     for (int j = 0; j < QIT; ++j) {
       const int idx = tid + j * DEC_THREADS;
       const int h = idx >> 6, i = idx & 63;
-      const int n0 = h < G ? qs.col_q + (hq0 + h) * DH : qs.col_k + hk * DH;
+      const int n0 = h < valid ? qs.col_q + (hq0 + h) * DH : qs.col_k + hk * DH;      // (padded head slots: k's columns, zeroed below)
       nch[2 * j] = n0 + i;
       nch[2 * j + 1] = n0 + i + 64;
     }
@@ -578,7 +587,12 @@ __global__ __launch_bounds__(DEC_THREADS, OMNI_FLASH_MIN_BLOCKS) void kv4_decode
       }
     }
 #pragma unroll
-    for (int j = 0; j < QIT; ++j) { qa[j] = val[2 * j]; qbv[j] = val[2 * j + 1]; }
+    for (int j = 0; j < QIT; ++j) {
+      const int h = (tid + j * DEC_THREADS) >> 6;
+      const bool pad = h >= valid && h < G;
+      qa[j] = pad ? (half_t)0.0f : val[2 * j];
+      qbv[j] = pad ? (half_t)0.0f : val[2 * j + 1];
+    }
     if (tid < DH) vcur_r = val[NE - 1];
   }
 
@@ -986,6 +1000,7 @@ __global__ __launch_bounds__(DEC_THREADS, OMNI_FLASH_MIN_BLOCKS) void kv4_decode
   __syncthreads();
   for (int oi = tid; oi < G * DH; oi += DEC_THREADS) {
     const int g = oi >> 7, qpos = oi & 127;
+    if (g >= valid) continue;      // (wave-uniform) a padded head slot stores nothing
     const int d = KV8 ? qpos : unperm_pos(qpos);
     float M = owns_cur ? scur[g] : -1e30f;
 #pragma unroll
@@ -1039,7 +1054,7 @@ __global__ __launch_bounds__(DEC_THREADS, OMNI_FLASH_MIN_BLOCKS) void kv4_decode
     FLASH_STAMP(27);
     if (red[0] != 0.0f && wave == DEC_WAVES - 1) {      // (the last wave: waves 0 / 1 go on to append the current token)
       const int i = hq0 * DH + lane * VT;                // 8 outputs per lane: G * 128 = up to 512 per workgroup
-      if (lane * VT < G * DH) {
+      if (lane * VT < valid * DH) {
         SrcAttnMergeT<true> src{p.part_ml, p.part_o, p.nsplit, p.num_heads, b};      // agent-scope loads: see row_kernels.h
         SrcAttnMergeT<true>::Raw raw;
         float x[VT];
@@ -1162,6 +1177,7 @@ __global__ __launch_bounds__(128) void kv4_decode_merge_kernel(half_t* __restric
 
 struct DecodePlan {
   int nsplit, split_tokens, g;
+  int tiles;               // head tiles (workgroups) per kv head: ceil(group / g)
   size_t lds_bytes;
 };
 
@@ -1171,10 +1187,22 @@ static DecodePlan plan_decode(int batch, int num_heads, int num_kv_heads, int ma
                               bool per_q_head = false, bool allow_g8 = false) {
   DecodePlan pl;
   const int group = num_heads / num_kv_heads;
-  pl.g = group >= 4 ? 4 : group;  // group in {1,2,4,8,...}
-  if (allow_g8 && group % 8 == 0) pl.g = 8;      // (the dense two-launch forms: one workgroup serves eight q heads)
+  if (group <= 2 || group % 4 == 0) {
+    pl.g = group >= 4 ? 4 : group;  // whole tiles
+    if (allow_g8 && group % 8 == 0) pl.g = 8;      // (the dense two-launch forms: one workgroup serves eight q heads)
+  } else {
+    // Any other ratio (3, 5, 6, 7, 10, ...): tiles of 4, or of 8 where the form has that instantiation and the group
+    // is larger than one tile of 4; the last tile of a kv head is ragged.  The tile with fewer padded head slots wins.
+    // Tiles of 8 never pad less than tiles of 4 (the paddings are -group mod 8 and -group mod 4), so the rule only
+    // ever decides ties, and a tie goes to the tile of 8: the same slots in half the workgroups, K / V fetched and
+    // unpacked once per eight head slots instead of once per four.  7 -> one tile of 8 (one padded slot), 5 and 6 likewise,
+    // 10 -> 4 + 4 + 2 (8 + 2 would pad six slots); without the G = 8 instantiation 7 -> 4 + 3.
+    const int pad4 = (4 - group % 4) % 4, pad8 = (8 - group % 8) % 8;
+    pl.g = (allow_g8 && group > 4 && pad8 <= pad4) ? 8 : 4;
+  }
   if (per_q_head) pl.g = 1;       // every q head walks its own page list
-  const int wgs_per_split = batch * num_kv_heads * (group / pl.g);
+  pl.tiles = (group + pl.g - 1) / pl.g;      // head tiles per kv head
+  const int wgs_per_split = batch * num_kv_heads * pl.tiles;
   // LDS bound of the two-pass kernel's score buffer; the kernels keep a window of 40 page pointers per split
   const int st_cap = 38 * tokens_per_block < 2048 ? 38 * tokens_per_block : 2048;
   const int max_s0 = (max_context + 63) / 64;
@@ -1404,8 +1432,6 @@ static int decode_common(void* out_f16, const void* q_f16, const void* k_f16, co
       tokens_per_block < 16 || (tokens_per_block & (tokens_per_block - 1)) != 0 || max_context < 1 ||
       rope_max_pos < 1)
     return OMNI_EINVAL;
-  const int group = num_heads / num_kv_heads;
-  if (group != 1 && group != 2 && group % 4 != 0) return OMNI_EINVAL;
   const DecodePlan pl = plan_decode(batch, num_heads, num_kv_heads, max_context, tokens_per_block, false, true);
   if ((long long)pl.nsplit * pl.split_tokens < max_context) return OMNI_EINVAL;
   const size_t need = (size_t)batch * num_heads * pl.nsplit * (DH + 2) * sizeof(float);
@@ -1415,6 +1441,7 @@ static int decode_common(void* out_f16, const void* q_f16, const void* k_f16, co
   a.q_stride = q_stride; a.kv_stride = kv_stride;
   a.kv_pointers = (const int64_t*)kv_pointers_i64; a.lengths = (const int*)lengths_i32;
   a.batch = batch; a.max_blocks = max_blocks; a.num_heads = num_heads; a.num_kv_heads = num_kv_heads;
+  a.group = num_heads / num_kv_heads;
   a.lay = make_layout(tokens_per_block, num_kv_heads);
   a.nsplit = pl.nsplit; a.split_tokens = pl.split_tokens;
   a.rope = (const float*)rope_cos_sin_f32; a.rope_max_pos = rope_max_pos;
@@ -1426,7 +1453,7 @@ static int decode_common(void* out_f16, const void* q_f16, const void* k_f16, co
   if (a.qs.slab && (a.qs.sstride != (long long)batch * a.qs.n || a.qs.col_q + num_heads * DH > a.qs.n ||
                     a.qs.col_k + num_kv_heads * DH > a.qs.n || a.qs.col_v + num_kv_heads * DH > a.qs.n))
     return OMNI_EINVAL;
-  dim3 grid(pl.nsplit, num_kv_heads * (group / pl.g), batch);
+  dim3 grid(pl.nsplit, num_kv_heads * pl.tiles, batch);
   hipStream_t st = (hipStream_t)stream;
   if (pl.lds_bytes > 160 * 1024) return OMNI_EINVAL;
   const bool pipe = pl.split_tokens > 5 * 32 * DEC_WAVES;      // a wave sweeps six or more 32-token tiles (the two batches the
@@ -1478,7 +1505,7 @@ extern "C" int omni_kv4_decode_attention_f16_amax(void* out_f16, void* amax_slot
   const int group = num_heads / num_kv_heads;
   const DecodePlan pl = plan_decode(batch, num_heads, num_kv_heads, max_context < 1 ? 1 : max_context,
                                     tokens_per_block < 16 ? 16 : tokens_per_block);
-  if (pl.nsplit < 2 || pl.g != 4 || group % 4 != 0) {      // one split (or an odd head group): the two-launch form
+  if (pl.nsplit < 2 || pl.g != 4 || group % 4 != 0) {      // one split (or an odd / ragged head group): the two-launch form
     int ns = 0;
     const int rc = decode_common(nullptr, q_f16, k_f16, v_f16, q_stride, kv_stride, kv_pointers_i64, lengths_i32, batch, max_blocks,
                                  num_heads, num_kv_heads, head_dim, tokens_per_block, max_context, rope_cos_sin_f32,
@@ -1495,13 +1522,14 @@ extern "C" int omni_kv4_decode_attention_f16_amax(void* out_f16, void* amax_slot
   if ((long long)pl.nsplit * pl.split_tokens < max_context) return OMNI_EINVAL;
   const size_t need = (size_t)batch * num_heads * pl.nsplit * (DH + 2) * sizeof(float);
   if (workspace_bytes < need) return OMNI_ENOMEM;
-  const int gy = num_kv_heads * (group / pl.g);
+  const int gy = num_kv_heads * pl.tiles;
   if (tickets_words < (size_t)batch * gy) return OMNI_ENOMEM;
   DecodeArgs a;
   a.out = (half_t*)out_f16; a.q = (const half_t*)q_f16; a.k = (const half_t*)k_f16; a.v = (const half_t*)v_f16;
   a.q_stride = q_stride; a.kv_stride = kv_stride;
   a.kv_pointers = (const int64_t*)kv_pointers_i64; a.lengths = (const int*)lengths_i32;
   a.batch = batch; a.max_blocks = max_blocks; a.num_heads = num_heads; a.num_kv_heads = num_kv_heads;
+  a.group = num_heads / num_kv_heads;
   a.lay = make_layout(tokens_per_block, num_kv_heads);
   a.nsplit = pl.nsplit; a.split_tokens = pl.split_tokens;
   a.rope = (const float*)rope_cos_sin_f32; a.rope_max_pos = rope_max_pos;
@@ -1589,8 +1617,6 @@ static int decode_fg_common(
       tokens_per_block < 16 || (tokens_per_block & (tokens_per_block - 1)) != 0 || max_context < 1 ||
       rope_max_pos < 1)
     return OMNI_EINVAL;
-  const int group = num_heads / num_kv_heads;
-  if (group != 1 && group != 2 && group % 4 != 0) return OMNI_EINVAL;
   DecodeArgs a;
   a.qs = armed_qs;
   int rc = fill_fg(&a.fg, streaming_kv_pointers_i64, retrieval_head_flags_i32, head_rank_table_i32, streaming_blocks,
@@ -1623,12 +1649,13 @@ static int decode_fg_common(
   a.q_stride = q_stride; a.kv_stride = kv_stride;
   a.kv_pointers = (const int64_t*)retrieval_kv_pointers_i64; a.lengths = (const int*)lengths_i32;
   a.batch = batch; a.max_blocks = retrieval_blocks; a.num_heads = num_heads; a.num_kv_heads = num_kv_heads;
+  a.group = num_heads / num_kv_heads;
   a.lay = make_layout(tokens_per_block, num_kv_heads);
   a.nsplit = pl.nsplit; a.split_tokens = pl.split_tokens;
   a.rope = (const float*)rope_cos_sin_f32; a.rope_max_pos = rope_max_pos;
   a.part_ml = (float*)workspace;
   a.part_o = a.part_ml + (size_t)batch * num_heads * pl.nsplit * 2;
-  dim3 grid(pl.nsplit, num_kv_heads * (group / pl.g), batch);
+  dim3 grid(pl.nsplit, num_kv_heads * pl.tiles, batch);
   hipStream_t st = (hipStream_t)stream;
   a.kv_qo = kv_qo; a.kv_oq = kv_oq;
   if (a.qs.slab && (a.qs.sstride != (long long)batch * a.qs.n || a.qs.col_q + num_heads * DH > a.qs.n ||

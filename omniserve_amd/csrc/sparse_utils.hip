@@ -63,6 +63,7 @@ struct SelArgs {
   int max_blocks, num_heads, num_kv_heads, num_retrieval_kv_heads, tpb, sub, padded;
   const float* rope; int rope_max_pos;
   int row_bytes;              // Dh/2 (KV4 pages) or Dh (KV8 pages)
+  int group, tiles;           // q heads per kv head; head tiles (workgroups along grid.y) per kv head = ceil(group / G)
 };
 
 // Page selector.  One workgroup per (block of SEL_PB pages, kv head, sequence) scores ALL q heads of the kv
@@ -70,6 +71,9 @@ struct SelArgs {
 // of 16 lanes (= one DPP row; 8 dims per lane, one 16-B load of kmax and of kmin) owns a sub-chunk; a team keeps
 // 8 sub-chunks = 16 loads in flight.  Per-lane sums run over e = 0..7 and the team butterfly over xor 8, 4, 2, 1
 // exactly as KVPageSelectorTemplate.hpp:482-493, so the fp32 sums (and the fp16 scores) are bit-identical.
+// A GQA group that is no whole number of head tiles (3, 5, 6, 7, 10, ...: the host picks G = 4 or 8) ends in a ragged tile of
+// `valid` < G real heads: a padded head slot holds a zero q (nothing is read for it), is scored like a real head and stores
+// nothing.  Groups of 1, 2, 4 and 8 are one whole tile of their own instantiation, as before.
 constexpr int SEL_PB = 32;     // pages per workgroup
 constexpr int SEL_UN = 8;      // sub-chunks in flight per team
 
@@ -83,7 +87,7 @@ template <int G>
 __global__ __launch_bounds__(256) void kv_page_selector_kernel(SelArgs p) {
   __shared__ __attribute__((aligned(16))) half_t q_lds[G * SDH];
   __shared__ int64_t page_lds[SEL_PB];
-  const int hk = blockIdx.y, b = blockIdx.z;
+  const int hk = blockIdx.y / p.tiles, tile = blockIdx.y - hk * p.tiles, b = blockIdx.z;
   if (p.retrieval_head_flags[hk] == 0) return;   // streaming heads: scores stay zero
   const int rank = p.head_rank_table[hk];
   const int tlen = p.lengths[b] - 1;
@@ -93,7 +97,8 @@ __global__ __launch_bounds__(256) void kv_page_selector_kernel(SelArgs p) {
   const int page0 = blockIdx.x * SEL_PB;
   const int c0 = page0 * subs;
   if (c0 >= n_sub) return;
-  const int h0 = hk * G;
+  const int h0 = hk * p.group + tile * G;
+  const int valid = min(G, p.group - tile * G);   // real heads of this tile
   if (tid < SEL_PB) {
     const int pg = page0 + tid;
     page_lds[tid] = (pg < p.max_blocks && pg * subs < n_sub) ? p.kv_pointers[(size_t)b * 2 * p.max_blocks + pg] : 0;
@@ -102,9 +107,10 @@ __global__ __launch_bounds__(256) void kv_page_selector_kernel(SelArgs p) {
     const int g = idx >> 6, i = idx & 63;
     const int rp = tlen < p.rope_max_pos ? tlen : p.rope_max_pos - 1;
     const float* cs = p.rope + (size_t)rp * SDH;
-    const half_t* src = p.q + (size_t)b * p.q_stride + (size_t)(h0 + g) * SDH;
+    const bool real = g < valid;
+    const half_t* src = p.q + (size_t)b * p.q_stride + (size_t)(h0 + (real ? g : 0)) * SDH;
     const float c = cs[2 * i], s = cs[2 * i + 1];
-    const float a = (float)src[i], bb = (float)src[i + 64];
+    const float a = real ? (float)src[i] : 0.0f, bb = real ? (float)src[i + 64] : 0.0f;
     const float t0 = c * a, t1 = s * bb, t2 = c * bb, t3 = s * a;
     q_lds[g * SDH + i] = (half_t)(t0 - t1);
     q_lds[g * SDH + i + 64] = (half_t)(t2 + t3);
@@ -145,7 +151,7 @@ __global__ __launch_bounds__(256) void kv_page_selector_kernel(SelArgs p) {
         acc += team_xor4(acc, lane);       // xor 4
         acc += lane_xor2(acc);
         acc += lane_xor1(acc);
-        if (part == 0 && ci < n_here) p.out[((size_t)b * p.num_heads + h0 + g) * p.padded + c0 + ci] = (half_t)acc;
+        if (part == 0 && ci < n_here && g < valid) p.out[((size_t)b * p.num_heads + h0 + g) * p.padded + c0 + ci] = (half_t)acc;
       }
     }
   }
@@ -339,18 +345,24 @@ extern "C" int omni_kv_page_selector(void* out_f16, const void* q_f16, int64_t q
   SelArgs a{(half_t*)out_f16, (const half_t*)q_f16, q_stride, (const int64_t*)kv_pointers_i64,
             (const int*)retrieval_head_flags_i32, (const int*)head_rank_table_i32, (const int*)lengths_i32,
             max_blocks, num_heads, num_kv_heads, num_retrieval_kv_heads, tokens_per_block, tokens_per_sub_chunk,
-            padded_sub_chunks, (const float*)rope_cos_sin_f32, rope_max_pos, kv_row_bytes};
+            padded_sub_chunks, (const float*)rope_cos_sin_f32, rope_max_pos, kv_row_bytes, 0, 1};
   const int group = num_heads / num_kv_heads;
+  // head tile: groups of 1, 2, 4, 8 are one whole tile; any other group runs tiles of 4 or 8, whichever pads fewer head slots
+  // in the last tile (a tie goes to 8: the page statistics are read once per eight heads): 3 -> 4; 5, 6, 7 -> 8; 10 -> 4 + 4 + 2
+  int g = group;
+  if (group != 1 && group != 2 && group != 4 && group != 8) g = (group > 4 && (8 - group % 8) % 8 <= (4 - group % 4) % 4) ? 8 : 4;
+  a.group = group;
+  a.tiles = (group + g - 1) / g;
   const int subs = tokens_per_block / tokens_per_sub_chunk;
   const int pages = (padded_sub_chunks + subs - 1) / subs;
   if (pages == 0) return OMNI_OK;
-  dim3 grid((pages + SEL_PB - 1) / SEL_PB, num_kv_heads, batch);
-  switch (group) {
+  dim3 grid((pages + SEL_PB - 1) / SEL_PB, num_kv_heads * a.tiles, batch);
+  switch (g) {
     case 1: hipLaunchKernelGGL(kv_page_selector_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, a); break;
     case 2: hipLaunchKernelGGL(kv_page_selector_kernel<2>, grid, dim3(256), 0, (hipStream_t)stream, a); break;
     case 4: hipLaunchKernelGGL(kv_page_selector_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, a); break;
     case 8: hipLaunchKernelGGL(kv_page_selector_kernel<8>, grid, dim3(256), 0, (hipStream_t)stream, a); break;
-    default: return OMNI_EINVAL;
+    default: return OMNI_EINVAL;      // (unreachable: g is one of the four above)
   }
   return omni_launch_status();
 }

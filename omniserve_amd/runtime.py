@@ -48,6 +48,13 @@ class LlamaConfig:
                            group_size=group_size)
 
     @staticmethod
+    def yi_34b(group_size=-1):
+        """Yi-34B: 56 q heads over 8 kv heads -- a GQA ratio of 7 (28 / 4 on a TP = 2 shard), which the decode attention serves
+        with ragged head tiles (csrc/kv_cache.hip).  hidden 7168 is past the level-3 gate (omni_gemm_rowfree_ok): level 2."""
+        return LlamaConfig(hidden=7168, inter=20480, heads=56, kv_heads=8, layers=60, vocab=64000, rope_theta=5000000.0,
+                           group_size=group_size)
+
+    @staticmethod
     def tiny():
         return LlamaConfig(hidden=512, inter=1024, heads=4, kv_heads=2, layers=2, vocab=512)
 
