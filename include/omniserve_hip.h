@@ -392,7 +392,13 @@ int omni_kv4_decode_attention(void* out_f16, const void* q_f16, const void* k_f1
  * q fp16 [Lq, Hq, 128], k,v fp16 [Lk, Hkv, 128] with token strides q/k/v_stride (elements; heads contiguous),
  * out fp16 [Lq, Hq, 128] contiguous; cu_seqlens int32 [B+1]; head_mask_type int32 [Hq] (0 dense, <0
  * streaming) and streaming_info int32 [2*Hq] = (sink, local) per head, or both NULL for all-dense.
- * mask = causal (bottom-right aligned) AND (dense OR k_pos < sink OR q_pos - k_pos < local).
+ * mask = causal (bottom-right aligned) AND (dense OR k_pos < sink OR q_pos - k_pos < local), with q_pos = row + len_k - len_q
+ * per sequence (len_q != len_k is fine; causal = 0 drops the first term only).
+ * A query row that sees no key -- q_pos < 0 under the causal mask, len_k = 0, an empty window -- is written as exact zeros
+ * (FlashAttention-2's convention); max_seqlen_q may exceed the longest sequence, sequences may be empty.
+ * sink and local may be any int32: each is clamped on the device to [0, (len_k >> g) + 1] units (g = 0 tokens, g = 7 blocks of
+ * 128 tokens) before it is shifted or multiplied, which changes no mask ("everything" = 2^31 - 1 is safe); negative entries are
+ * treated as 0.  All pointers are non-NULL even when a side has no token; len_q + len_k + 256 < 2^31 per sequence.
  * -------------------------------------------------------------------------------------------- */
 int omni_prefill_attention(void* out_f16, const void* q_f16, const void* k_f16, const void* v_f16,
                            int64_t q_stride, int64_t k_stride, int64_t v_stride,
@@ -401,7 +407,8 @@ int omni_prefill_attention(void* out_f16, const void* q_f16, const void* k_f16, 
                            const void* head_mask_type_i32, const void* streaming_info_i32, void* stream);
 /* Replaces block_sparse_attn.block_streaming_attn_func (imported at ctx_attn_func.py:3-7, wrapped at :47-59; no caller upstream):
  * omni_prefill_attention (causal) with streaming_info = (sink, local) per q head counted in blocks of 128 tokens --
- * mask = causal AND (dense OR k_pos / 128 < sink OR q_pos / 128 - k_pos / 128 < local).  Both tables are required. */
+ * mask = causal AND (dense OR k_pos / 128 < sink OR q_pos / 128 - k_pos / 128 < local) (floor division; q_pos as above).  Both
+ * tables are required.  Zero rows and the (sink, local) clamp as above. */
 int omni_prefill_attention_block_streaming(void* out_f16, const void* q_f16, const void* k_f16, const void* v_f16,
                                            int64_t q_stride, int64_t k_stride, int64_t v_stride,
                                            const void* cu_seqlens_q_i32, const void* cu_seqlens_k_i32, int batch,

@@ -15,6 +15,10 @@ def _run(q, k, v, cu_q, cu_k, max_q, causal, head_mask_type, streaming_info, wha
     if cu_q.dtype != torch.int32 or cu_k.dtype != torch.int32:
         raise RuntimeError("%s: cu_seqlens must be int32" % what)
     out = torch.empty((q.shape[0], q.shape[1], 128), dtype=torch.float16, device=q.device)
+    if q.shape[0] == 0 or k.shape[0] == 0:
+        # no query, or no key in the whole batch (k / v have no storage to point at): every row is one that sees no key,
+        # which the kernel writes as zeros (include/omniserve_hip.h); there is nothing to launch
+        return out.zero_()
     hm = head_mask_type.data_ptr() if head_mask_type is not None else None
     si = streaming_info.data_ptr() if streaming_info is not None else None
     if block:

@@ -6,7 +6,8 @@
 //   block_sparse_attn.token_streaming_attn_func(q,k,v,cu_q,cu_k,head_mask_type,streaming_info,max_q,max_k)
 // Semantics (inferred, the package is not vendored): softmax(q k^T / sqrt(Dh) + mask) v per
 // sequence and q head, GQA by head index division; mask = causal (bottom-right aligned) and, for heads with
-// head_mask_type < 0, additionally (k_pos < sink  OR  q_pos - k_pos < local).
+// head_mask_type < 0, additionally (k_pos < sink  OR  q_pos - k_pos < local).  q_pos = row + len_k - len_q; a row that sees no
+// key at all (q_pos < 0 under the causal mask, len_k = 0, an empty window) is written as exact zeros (FlashAttention-2's convention).
 //
 // Structure (flash-attention, online softmax, matrix cores): a workgroup of 8 waves owns 128 query rows (16 per
 // wave = one 16-row MFMA block; ~120 VGPRs per wave, so two workgroups = 4 waves per SIMD cover the softmax VALU
@@ -71,6 +72,14 @@ struct PrefillArgs {
 // query at (bottom-right aligned) position qpos.  g = 0: qpos - local + 1 (the last `local` tokens, itself included); g = 7:
 // the first token of block (qpos >> 7) - local + 1 (the query's own 128-token block and the local - 1 blocks before it).
 __device__ __forceinline__ int first_local_key(int qpos, int local, int g) { return ((qpos >> g) - local + 1) * (1 << g); }
+// A (sink, local) entry as the kernels use it: clamped to [0, (len_k >> g) + 1] units of 1 << g tokens, once per workgroup and
+// before any shift or multiply.  (len_k >> g) + 1 units already cover every key of the sequence -- sink: ((len_k >> g) + 1) << g
+// > len_k; local: qpos <= len_k - 1, so first_local_key <= 0 -- hence the clamp changes no element predicate and no tile
+// predicate (skipped / full / win_lo all use the clamped pair), and it keeps sink << g and first_local_key inside int32 for
+// every int32 entry: |first_local_key| <= len_q + len_k + (2 << g).  Unclamped, the block form wrapped from 1 << 24 on ("everything"
+// put the window behind the query: rows of zeros), the token form for queries at negative positions (len_q > len_k).  Negative
+// entries count as 0: no sink; no local key at or before the query.
+__device__ __forceinline__ int window_units(int entry, int len_k, int g) { return min(max(entry, 0), (len_k >> g) + 1); }
 
 // 1-D grid: workgroups are dealt round-robin to the 8 XCDs (private L2s; the dispatch is static: workgroup w runs on XCD
 // w % 8 whatever the others are doing).  All q heads of a kv head share an XCD's L2, so a K/V tile is fetched from the
@@ -136,8 +145,8 @@ void prefill_attn_kernel(PrefillArgs p) {
   const int off = len_k - len_q;                                // bottom-right aligned causal mask
   const bool streaming = p.head_mask_type != nullptr && p.head_mask_type[h] < 0;
   const int gl = p.gran_log2;
-  const int sink = streaming ? p.streaming_info[2 * h] << gl : 0;      // in tokens
-  const int local = streaming ? p.streaming_info[2 * h + 1] : 0;       // in units of 1 << gl tokens
+  const int sink = streaming ? window_units(p.streaming_info[2 * h], len_k, gl) << gl : 0;      // in tokens
+  const int local = streaming ? window_units(p.streaming_info[2 * h + 1], len_k, gl) : 0;       // in units of 1 << gl tokens
   const float scale2 = 0.08838834764831845f * 1.4426950408889634f;   // log2(e)/sqrt(128): scores in the exp2 domain
 
   // B operand of S^T = K Q^T: Q[row][32s + 8*l4 + (0..7)] for the wave's two row blocks
@@ -410,8 +419,8 @@ void prefill_attn_pp_kernel(PrefillArgs p) {
   const int off = len_k - len_q;
   const bool streaming = p.head_mask_type != nullptr && p.head_mask_type[h] < 0;
   const int gl = p.gran_log2;
-  const int sink = streaming ? p.streaming_info[2 * h] << gl : 0;
-  const int local = streaming ? p.streaming_info[2 * h + 1] : 0;
+  const int sink = streaming ? window_units(p.streaming_info[2 * h], len_k, gl) << gl : 0;
+  const int local = streaming ? window_units(p.streaming_info[2 * h + 1], len_k, gl) : 0;
   const float scale2 = 0.08838834764831845f * 1.4426950408889634f;
   const int qrow = q0 + l15;
   v8h qb[4];
@@ -646,8 +655,8 @@ void prefill_attn32_kernel(PrefillArgs p) {
   const int off = len_k - len_q;
   const bool streaming = p.head_mask_type != nullptr && p.head_mask_type[h] < 0;
   const int gl = p.gran_log2;
-  const int sink = streaming ? p.streaming_info[2 * h] << gl : 0;      // in tokens
-  const int local = streaming ? p.streaming_info[2 * h + 1] : 0;       // in units of 1 << gl tokens
+  const int sink = streaming ? window_units(p.streaming_info[2 * h], len_k, gl) << gl : 0;      // in tokens
+  const int local = streaming ? window_units(p.streaming_info[2 * h + 1], len_k, gl) : 0;       // in units of 1 << gl tokens
   const float scale2 = 0.08838834764831845f * 1.4426950408889634f;
   const int qrow = q_first + wave * 32 + l32;               // this lane's query row (lanes l and l + 32 share it)
 

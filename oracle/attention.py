@@ -21,7 +21,8 @@ def streaming_mask(qi, ki, sink, local, block=1):
 
 def varlen_attention(q, k, v, cu_q, cu_k, causal=True, head_mask_type=None, streaming_info=None, block=1):
     """q [Lq,Hq,D], k,v [Lk,Hkv,D] fp16 -> out fp16 [Lq,Hq,D].  f64 softmax reference.  block: granularity of streaming_info
-    (streaming_mask)."""
+    (streaming_mask).  A query row that sees no key at all (len_k < len_q under the bottom-right aligned causal mask, len_k = 0)
+    is exact zeros: FlashAttention-2's convention, and what the kernel's l > 0 ? 1 / l : 0 gives."""
     q = np.asarray(q, np.float16); k = np.asarray(k, np.float16); v = np.asarray(v, np.float16)
     Lq, Hq, D = q.shape
     Hk = k.shape[1]
@@ -44,18 +45,26 @@ def varlen_attention(q, k, v, cu_q, cu_k, causal=True, head_mask_type=None, stre
             if head_mask_type is not None and int(head_mask_type[h]) < 0:
                 sink, local = int(streaming_info[2 * h]), int(streaming_info[2 * h + 1])
                 mask &= streaming_mask(qi, ki, sink, local, block)
-            s = np.where(mask, s, -np.inf)
-            m = s.max(axis=1, keepdims=True)
-            p = np.exp(s - m)
-            p = np.where(mask, p, 0.0)
-            o = (p @ v[k0:k1, h // g].astype(np.float64)) / p.sum(axis=1, keepdims=True)
-            out[q0:q1, h] = o.astype(np.float16)
+            out[q0:q1, h] = _masked_softmax_v(s, mask, v[k0:k1, h // g])
     return out
 
 
+def _masked_softmax_v(s, mask, v):
+    """softmax over the keys `mask` lets through (f64) times v -> fp16; rows without a visible key are exact zeros."""
+    if s.shape[1] == 0:
+        return np.zeros((s.shape[0], v.shape[-1]), np.float16)
+    s = np.where(mask, s, -np.inf)
+    m = s.max(axis=1, keepdims=True)
+    m = np.where(np.isfinite(m), m, 0.0)              # a row with no key: exp(-inf - 0) = 0 everywhere
+    p = np.where(mask, np.exp(s - m), 0.0)
+    den = p.sum(axis=1, keepdims=True)
+    o = (p @ v.astype(np.float64)) / np.where(den > 0.0, den, 1.0)
+    return o.astype(np.float16)
+
+
 def varlen_attention_rows(q, k, v, cu_q, cu_k, rows, causal=True, head_mask_type=None, streaming_info=None,
-                          heads=None, chunk=256):
-    """The same reference restricted to the global query rows `rows` (sorted int array) and the q heads `heads`
+                          heads=None, chunk=256, block=1):
+    """The same reference (zero rows and `block` included) restricted to the global query rows `rows` (sorted int array) and the q heads `heads`
     (default: all) -> fp16 [len(rows), len(heads), D].  Evaluated chunk by chunk over the query rows and, for a
     Lambda-masked head, only over the keys the mask lets through, so that long sequences (L = 16K ... 64K) stay
     within seconds and a few hundred MB of host memory: the tests compare a dense sample of rows of a long case."""
@@ -74,14 +83,14 @@ def varlen_attention_rows(q, k, v, cu_q, cu_k, rows, causal=True, head_mask_type
         for c0 in range(0, len(sel), chunk):
             idx = sel[c0:c0 + chunk]
             qi = (rows[idx] - q0 + off)[:, None]                     # key position a query may look back from
-            hi = int(qi.max()) + 1 if causal else (k1 - k0)
+            hi = max(int(qi.max()) + 1, 0) if causal else (k1 - k0)
             for hn, h in enumerate(heads):
                 streaming = head_mask_type is not None and int(head_mask_type[h]) < 0
                 if streaming:
                     sink, local = int(streaming_info[2 * h]), int(streaming_info[2 * h + 1])
-                    lo = max(min(sink, hi), int(qi.min()) - local + 1)
-                    ki = np.concatenate([np.arange(0, min(sink, hi)), np.arange(max(lo, 0), hi)])
-                    ki = np.unique(ki)
+                    nsink = min(sink * block, hi)                                     # Python integers: nothing wraps
+                    lo = min(max(nsink, (int(qi.min()) // block - local + 1) * block), hi)
+                    ki = np.concatenate([np.arange(0, nsink), np.arange(lo, hi)])
                 else:
                     ki = np.arange(0, hi)
                 kk = k[k0 + ki, h // g].astype(np.float64)
@@ -90,10 +99,6 @@ def varlen_attention_rows(q, k, v, cu_q, cu_k, rows, causal=True, head_mask_type
                 if causal:
                     mask &= ki[None, :] <= qi
                 if streaming:
-                    mask &= (ki[None, :] < sink) | ((qi - ki[None, :]) < local)
-                s = np.where(mask, s, -np.inf)
-                m = s.max(axis=1, keepdims=True)
-                pr = np.where(mask, np.exp(s - m), 0.0)
-                o = (pr @ v[k0 + ki, h // g].astype(np.float64)) / pr.sum(axis=1, keepdims=True)
-                out[idx, hn] = o.astype(np.float16)
+                    mask &= streaming_mask(qi, ki[None, :], sink, local, block)
+                out[idx, hn] = _masked_softmax_v(s, mask, v[k0 + ki, h // g])
     return out

@@ -179,6 +179,84 @@ def test_prefill_attention_oracle_block_streaming_mask():      # block_streaming
     assert not m1[130, :128].any() and m1[130, 128:131].all()
 
 
+# ---- prefill attention off the equal-length causal path: the cases of tests/prefill_edge_cases.py ------------------------
+def test_prefill_attention_oracle_two_keys_closed_form():
+    """Two keys, answers by hand.  Sequence 0: len_q 1, len_k 2 (off = +1), q.k0 - q.k1 = sqrt(128) * ln 3, so the dense head's
+    softmax is (3/4, 1/4); the streaming head with the window (0, 0) sees no key: exact zeros.  Sequence 1: len_q 2, len_k 1
+    (off = -1): row 0 is in front of the only key (zeros), row 1 sees it alone (v itself)."""
+    q = np.zeros((3, 2, 128), F16); k = np.zeros((3, 1, 128), F16); v = np.zeros((3, 1, 128), F16)
+    q[:, :, 0] = 4.0
+    k[0, 0, 0], k[1, 0, 0] = 3.0, 1.0             # scores 12 / sqrt(128) and 4 / sqrt(128)
+    k[2, 0, 0] = -7.0
+    v[0, 0, :2], v[1, 0, :2], v[2, 0, :2] = (1.0, 8.0), (3.0, -8.0), (0.5, 0.25)
+    cu_q, cu_k = np.array([0, 1, 3], np.int32), np.array([0, 2, 3], np.int32)
+    hm, si = np.array([0, -1], np.int32), np.array([0, 0, 0, 0], np.int32)
+    p0 = 1.0 / (1.0 + np.exp(-8.0 / np.sqrt(128.0)))
+    want = np.zeros((3, 2, 128), np.float64)
+    want[0, 0, :2] = p0 * 1.0 + (1 - p0) * 3.0, p0 * 8.0 - (1 - p0) * 8.0
+    want[2, 0, :2] = 0.5, 0.25
+    for block in (1, 128):
+        out = oa.varlen_attention(q, k, v, cu_q, cu_k, True, hm, si, block=block)
+        rows = oa.varlen_attention_rows(q, k, v, cu_q, cu_k, np.arange(3), True, hm, si, block=block)
+        assert np.array_equal(out.view(np.uint16), rows.view(np.uint16))
+        assert np.array_equal(out, want.astype(F16)), (out[:, :, :2], want[:, :, :2])      # (0, 0) blocks: no key either
+        assert not out[0, 1].any() and not out[1].any()          # exact zeros, not NaN
+    # the same batch, non-causal: every row of the dense head sees its sequence's keys
+    nc = oa.varlen_attention(q, k, v, cu_q, cu_k, False)
+    assert np.array_equal(nc[0, 0], want[0, 0].astype(F16)) and np.array_equal(nc[1, 0], v[2, 0]) and np.array_equal(nc[2, 0], v[2, 0])
+
+
+def test_prefill_attention_oracle_rows_equal_full_on_every_edge_case():
+    """varlen_attention_rows (every row asked for) == varlen_attention bit for bit on each case family of the GPU edge tests,
+    rows without a visible key are exact zeros in both, and nothing is NaN."""
+    from tests import prefill_edge_cases as pe
+    cases = pe.all_cases()
+    assert len({c["name"] for c in cases}) == len(cases)
+    nzero = 0
+    for c in cases:
+        q, k, v, cu_q, cu_k = pe.inputs(c)
+        full = pe.reference(c)
+        rows = oa.varlen_attention_rows(q, k, v, cu_q, cu_k, np.arange(q.shape[0]), c["causal"], c["hm"], c["si"], block=c["block"])
+        assert np.array_equal(full.view(np.uint16), rows.view(np.uint16)), c["name"]
+        assert np.isfinite(full.astype(np.float32)).all(), c["name"]
+        z = pe.zero_rows(c)
+        assert not full[z].any(), c["name"]
+        nzero += int(z.sum())
+    assert nzero > 0
+    c = {c["name"]: c for c in cases}["a-q50-k20-dense"]
+    assert pe.zero_rows(c)[:30].all() and not pe.zero_rows(c)[30:].any()      # len_q 50, len_k 20: the first 30 rows
+
+
+def test_prefill_attention_oracle_everything_window_is_dense_causal():
+    """sink or local of 1 << 24 ... 2**31 - 1, in tokens or in 128-token blocks: Python integers, nothing wraps, and the
+    result is dense causal attention bit for bit."""
+    from tests import prefill_edge_cases as pe
+    dense = None
+    for c in pe.family_d():
+        q, k, v, cu_q, cu_k = pe.inputs(c)
+        if dense is None:
+            dense = oa.varlen_attention(q, k, v, cu_q, cu_k, True)
+        assert np.array_equal(pe.reference(c).view(np.uint16), dense.view(np.uint16)), c["name"]
+
+
+def test_prefill_softmax_stress_inputs_have_the_ramp_they_claim():
+    """Family e: along the dense heads' causal rows, the maximum score of each full 64-key tile beats the previous tile's by
+    more than 20 (natural-log units) for the ascending ramp; for the descending ramp the first tile holds the row maximum by
+    more than 20."""
+    from tests import prefill_edge_cases as pe
+    for c in pe.family_e():
+        if c["ramp"] is None:
+            continue
+        q, k, v, _, _ = pe.inputs(c)
+        assert (q.astype(np.float64)[:, :, ::2].sum(-1) - q.astype(np.float64)[:, :, 1::2].sum(-1)).min() / np.sqrt(128) >= 32
+        s = np.einsum("qd,kd->qk", q[:, 0].astype(np.float64), k[:, 0].astype(np.float64)) / np.sqrt(128.0)
+        for row in (127, 300, 699):
+            tiles = [s[row, t:t + 64].max() for t in range(0, row + 1 - 63, 64)]
+            steps = np.diff(tiles)
+            assert len(steps) >= 1
+            assert (steps > 20).all() if c["ramp"] == "ascending" else (tiles[0] - max(tiles[1:]) > 20 and (steps < -20).all())
+
+
 # ---- the overloads off the Llama path (oracle/elementwise.py, second half) ----------------------------------------------
 def test_fma32_is_a_single_rounding():       # nvcc contracts a*b+c (fused_kernels.cu:35-36, layernorm_kernels.cu:384-391)
     from fractions import Fraction
