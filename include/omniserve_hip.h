@@ -360,6 +360,21 @@ int omni_kv4_prefill_write(void* qkv_f16, const void* seq_lens_i32, const void* 
                            int tokens_per_block, const void* rope_cos_sin_f32, int rope_max_pos,
                            int max_position_embeddings, void* stream);
 
+/* Project extension (chunked prefill, multi-turn, prefix reuse): omni_kv4_prefill_write for tokens that CONTINUE a sequence.
+ * Same arguments plus past_lens int32 [B] (device): token i of sequence b in this call is position past_lens[b] + i -- its
+ * RoPE row is that position, its page pos >> log2(tokens_per_block), its slot pos & (tokens_per_block - 1).  seq_lens,
+ * padding_offsets and max_seq_len describe the call's own tokens, as above.  Quantisation, page bytes, tails and the
+ * in-place RoPE of q and k are omni_kv4_prefill_write's; with past_lens all zero the two write the same bytes.
+ * rope_cos_sin must cover max(past + len) rows: the caller that knows the past lengths checks it (fused_ext does); the
+ * entry refuses rope_max_pos < max_seq_len, and the device clamps the row as omni_kv4_prefill_write does.
+ * max_position_embeddings keeps its meaning with the sequence length past + len.  Dense KV4 + zeros only (no
+ * fine-grained / per-tensor form). */
+int omni_kv4_prefill_write_at(void* qkv_f16, const void* seq_lens_i32, const void* past_lens_i32,
+                              const void* padding_offsets_i32, const void* kv_pointers_i64, int tokens, int batch,
+                              int max_blocks, int num_heads, int num_kv_heads, int head_dim, int max_seq_len,
+                              int tokens_per_block, const void* rope_cos_sin_f32, int rope_max_pos,
+                              int max_position_embeddings, void* stream);
+
 /* Tuning hook: force the number of KV splits of omni_kv4_decode_attention (0 = heuristic). */
 void omni_kv4_decode_set_split_override(int nsplit);
 
@@ -414,6 +429,22 @@ int omni_prefill_attention_block_streaming(void* out_f16, const void* q_f16, con
                                            const void* cu_seqlens_q_i32, const void* cu_seqlens_k_i32, int batch,
                                            int max_seqlen_q, int num_heads, int num_kv_heads, int head_dim,
                                            const void* head_mask_type_i32, const void* streaming_info_i32, void* stream);
+/* Project extension: causal prefill attention that continues from the KV4 page cache.  Per sequence b and q head the keys /
+ * values are  [0, past_lens[b])  from the pages of kv_pointers (int64 [B, 2, max_blocks]; dequantised with the reference's
+ * fp16 fma(u4, scale, h(-scale*zero)), as omni_kv4_decode_attention does)  followed by the call's own len_q = cu_seqlens_q[b+1]
+ * - cu_seqlens_q[b] tokens as un-quantised fp16 k_new / v_new [Lq, Hkv, 128] (token strides in elements, heads contiguous:
+ * views of the qkv buffer the writer has already rotated).  The page slots of [past, past + len_q) are NOT read, whatever
+ * they hold (the writer may have run).  Mask: query i sees every past key and the new keys <= i (causal, bottom-right
+ * aligned); softmax scale 1/sqrt(128); GQA by head index division, any num_heads % num_kv_heads == 0.  out fp16 [Lq, Hq, 128]
+ * contiguous.  Sequences with len_q = 0 are skipped; max_seqlen_q may exceed the longest sequence; past_lens all zero = the
+ * causal attention of omni_prefill_attention on the fresh tensors.  All heads are dense (no streaming heads, no
+ * non-causal form).  -EINVAL: head_dim != 128, tokens_per_block not a power of two >= 16, num_heads % num_kv_heads != 0,
+ * k / v byte strides >= 2^32.  batch = 0 or max_seqlen_q = 0 (no query token) returns 0 and launches nothing. */
+int omni_prefill_attention_paged_kv4(void* out_f16, const void* q_f16, const void* k_new_f16, const void* v_new_f16,
+                                     int64_t q_stride, int64_t k_stride, int64_t v_stride,
+                                     const void* cu_seqlens_q_i32, const void* past_lens_i32,
+                                     const void* kv_pointers_i64, int batch, int max_blocks, int tokens_per_block,
+                                     int max_seqlen_q, int num_heads, int num_kv_heads, int head_dim, void* stream);
 /* Tuning / test hook: 0 = 16 query rows per wave (16x16x32 MFMA, default), 1 = 32 rows per wave (32x32x16 MFMA), 2 = the 16-row
  * form on the 8-wave ping-pong schedule (waves 4-7 one segment behind waves 0-3; same results within the attention tolerance). */
 void omni_prefill_set_variant(int variant);

@@ -497,3 +497,84 @@ def norm_gemm_fused(codes, residual, gamma, input_sum, scaling, epsilon, lin, ou
             lin.s2_scales.data_ptr(), lin.s1_scales.data_ptr(), out.data_ptr(), out.stride(0), _ptr(amax), sync.data_ptr(),
             err.data_ptr(), M, N, K, _ptr(clk), st)
     _lib.check(rc, "fused_ext.norm_gemm_fused")
+
+
+# ---- chunked / multi-turn prefill: the prefill pair that continues from the KV4 pages ----------------
+def _check_lens(t, n, what, name):
+    if t.dtype != torch.int32 or t.dim() != 1 or t.shape[0] != n or not t.is_contiguous():
+        raise RuntimeError("%s: %s must be a contiguous int32 [%d] tensor" % (what, name, n))
+
+
+def kv4_prefill_write_at(qkv, seq_lens, past_lens, padding_offset, kv_pointers, head_num, kv_head_num, max_seq_len,
+                         tokens_per_block, max_total_len, rotary_base=10000.0, rope_scale=1.0, cyclic_len=1 << 20):
+    """apply_bias_rope_update_kv_cache (dense KV4 + zeros) for tokens that continue a sequence: token i of sequence b is
+    position past_lens[b] + i (RoPE row, page, slot).  qkv fp16 [tokens, (Hq+2Hkv)*128] (q and k rotated in place), seq_lens /
+    past_lens int32 [B] on the device, padding_offset = compute_padding_offsets(cu_seqlens, max_seq_len, tokens).
+    max_total_len: the host's bound on max(past + len) -- the RoPE table is built for it (the lengths themselves stay on the
+    device).  Same page bytes as the plain writer would leave for the same positions."""
+    from ..rope import rope_table
+    what = "fused_ext.kv4_prefill_write_at"
+    _lib.require_cuda(qkv, seq_lens, past_lens, padding_offset, kv_pointers)
+    width = (head_num + 2 * kv_head_num) * 128
+    if qkv.dtype != torch.float16 or qkv.dim() != 2 or qkv.shape[1] != width or not qkv.is_contiguous():
+        raise RuntimeError("%s: qkv must be contiguous fp16 [tokens, (Hq+2Hkv)*128]" % what)
+    B = seq_lens.shape[0]
+    _check_lens(seq_lens, B, what, "seq_lens")
+    _check_lens(past_lens, B, what, "past_lens")
+    _check_lens(padding_offset, qkv.shape[0], what, "padding_offset")
+    if kv_pointers.dtype != torch.int64 or kv_pointers.dim() != 3 or kv_pointers.shape[0] != B or kv_pointers.shape[1] != 2 \
+            or not kv_pointers.is_contiguous():
+        raise RuntimeError("%s: kv_pointers must be a contiguous int64 [B,2,blocks] tensor" % what)
+    if int(max_total_len) < int(max_seq_len) or int(max_total_len) > kv_pointers.shape[2] * int(tokens_per_block):
+        raise RuntimeError("%s: max_total_len must cover the call's tokens and fit the block table" % what)
+    table = rope_table(int(max_total_len), 128, float(rotary_base), float(rope_scale), qkv.device)
+    rc = _lib.lib().omni_kv4_prefill_write_at(
+        qkv.data_ptr(), seq_lens.data_ptr(), past_lens.data_ptr(), padding_offset.data_ptr(), kv_pointers.data_ptr(),
+        qkv.shape[0], B, kv_pointers.shape[2], int(head_num), int(kv_head_num), 128, int(max_seq_len),
+        int(tokens_per_block), table.data_ptr(), table.shape[0], int(cyclic_len), _lib.current_stream())
+    _lib.check(rc, what)
+
+
+def prefill_attention_paged_kv4(q, k_new, v_new, cu_seqlens_q, past_lens, kv_pointers, tokens_per_block, max_seqlen_q,
+                                causal=True, head_mask_type=None, streaming_info=None):
+    """Causal prefill attention whose first past_lens[b] keys / values of sequence b come from the KV4 pages (fp16 dequant, as the
+    decode attention reads them) and whose last len_q keys / values are the call's own fp16 k_new / v_new -- the page slots of
+    those tokens are not read.  q [Lq, Hq, 128], k_new / v_new [Lq, Hkv, 128] fp16 with contiguous heads (token-strided views of
+    the qkv buffer, already rotated by kv4_prefill_write_at); cu_seqlens_q int32 [B+1], past_lens int32 [B], kv_pointers int64
+    [B, 2, blocks].  -> out fp16 [Lq, Hq, 128].  Dense heads and the causal mask only."""
+    what = "fused_ext.prefill_attention_paged_kv4"
+    if not causal:
+        raise NotImplementedError("%s: only the causal mask is implemented" % what)
+    if head_mask_type is not None or streaming_info is not None:
+        raise NotImplementedError("%s: streaming heads are not implemented (all heads are dense)" % what)
+    _lib.require_cuda(q, k_new, v_new, cu_seqlens_q, past_lens, kv_pointers)
+    if q.dtype != torch.float16 or q.dim() != 3 or q.shape[-1] != 128:
+        raise RuntimeError("%s: q must be fp16 [tokens, heads, 128]" % what)
+    for t in (k_new, v_new):
+        if t.dtype != torch.float16 or t.dim() != 3 or t.shape[-1] != 128 or t.shape[0] != q.shape[0]:
+            raise RuntimeError("%s: k_new / v_new must be fp16 [tokens, kv heads, 128] with q's token count" % what)
+    for t in (q, k_new, v_new):
+        if t.stride(2) != 1 or t.stride(1) != 128:
+            raise RuntimeError("%s: heads must be contiguous (token-strided views are fine)" % what)
+    if k_new.shape[1] != v_new.shape[1] or k_new.shape[1] < 1 or q.shape[1] % k_new.shape[1] != 0:
+        raise RuntimeError("%s: the q heads must be a multiple of the kv heads" % what)
+    if cu_seqlens_q.dim() != 1 or cu_seqlens_q.shape[0] < 1:
+        raise RuntimeError("%s: cu_seqlens_q must be int32 [B+1]" % what)
+    B = cu_seqlens_q.shape[0] - 1
+    _check_lens(cu_seqlens_q, B + 1, what, "cu_seqlens_q")
+    _check_lens(past_lens, B, what, "past_lens")
+    if kv_pointers.dtype != torch.int64 or kv_pointers.dim() != 3 or kv_pointers.shape[0] != B or kv_pointers.shape[1] != 2 \
+            or not kv_pointers.is_contiguous():
+        raise RuntimeError("%s: kv_pointers must be a contiguous int64 [B,2,blocks] tensor" % what)
+    tpb = int(tokens_per_block)
+    if tpb < 16 or tpb & (tpb - 1):
+        raise RuntimeError("%s: tokens_per_block must be a power of two >= 16" % what)
+    out = torch.empty((q.shape[0], q.shape[1], 128), dtype=torch.float16, device=q.device)
+    if q.shape[0] == 0 or B == 0:
+        return out
+    rc = _lib.lib().omni_prefill_attention_paged_kv4(
+        out.data_ptr(), q.data_ptr(), k_new.data_ptr(), v_new.data_ptr(), q.stride(0), k_new.stride(0), v_new.stride(0),
+        cu_seqlens_q.data_ptr(), past_lens.data_ptr(), kv_pointers.data_ptr(), B, kv_pointers.shape[2], tpb,
+        int(max_seqlen_q), q.shape[1], k_new.shape[1], 128, _lib.current_stream())
+    _lib.check(rc, what)
+    return out

@@ -17,6 +17,7 @@
 //     accumulate in fp32.
 #include "common.h"
 #include "row_kernels.h"
+#include "kv4_dequant.h"
 
 namespace omni {
 
@@ -90,7 +91,7 @@ __global__ __launch_bounds__(256) void kv4_prefill_write_kernel(
     half_t* __restrict__ qkv, const int* __restrict__ seq_lens, const int* __restrict__ padding_offsets,
     const int64_t* __restrict__ kv_pointers, int tokens, int max_blocks, int num_heads, int num_kv_heads,
     int max_seq_len, KvLayout lay, const float* __restrict__ rope, int rope_max_pos, int cyclic_len, FgArgs fg,
-    const float* __restrict__ kv_oq) {
+    const float* __restrict__ kv_oq, const int* __restrict__ past_lens) {
   constexpr int RB = KV8 ? DH : ROW_BYTES;
   const int slots_per_token = num_heads + num_kv_heads;
   const long long slot_id = (long long)blockIdx.x * 16 + (threadIdx.x >> 4);
@@ -100,9 +101,14 @@ __global__ __launch_bounds__(256) void kv4_prefill_write_kernel(
   const int hs = (int)(slot_id % slots_per_token);
   const int g = tok + padding_offsets[tok];
   const int b = g / max_seq_len;
-  const int pos = g % max_seq_len;
-  const int actual_len = seq_lens[b];
+  int pos = g % max_seq_len;
+  int actual_len = seq_lens[b];
   if (pos >= actual_len) return;  // padding row (cannot happen with consistent metadata)
+  if (past_lens) {                // omni_kv4_prefill_write_at: the call's tokens continue a sequence whose first past[b] tokens
+    const int past = past_lens[b];   // are in the pages already: position (RoPE row, page, slot) = past + index in the call
+    pos += past;
+    actual_len += past;
+  }
   const int row_elems = (num_heads + 2 * num_kv_heads) * DH;
   half_t* row = qkv + (size_t)tok * row_elems;
   const bool is_kv = hs >= num_heads;
@@ -224,47 +230,7 @@ __global__ __launch_bounds__(256) void kv4_prefill_write_kernel(
 // ------------------------------------------------------------------------------------------
 // Decode attention
 // ------------------------------------------------------------------------------------------
-// unpack 16 packed bytes (32 codes) and dequantise with fp16 fma(u, scale, c), c = h(-scale*zero).
-// Output order per 32-bit word of 8 codes e0..e7: half2 pairs (e0,e4) (e1,e5) (e2,e6) (e3,e7),
-// i.e. out[w*4 + j] = {e_j, e_{j+4}} of word w (the q operand is loaded in the same order).
-// (x & mask) | magic in one VALU op.  VOP3 on gfx9 takes one scalar operand, so the magic lives in a VGPR; the
-// compiler emits v_and + v_or with two literals otherwise (64 extra ops per 32-token tile of the decode kernels).
-__device__ __forceinline__ uint32_t and_or(uint32_t x, uint32_t mask, uint32_t magic) {
-  uint32_t r;
-  asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(r) : "v"(x), "s"(mask), "v"(magic));
-  return r;
-}
-
-template <bool CHEAP = false>
-__device__ __forceinline__ void kv4_dequant16(const uint4 raw, v2h scale2, v2h c2, v2h out[16]) {
-  const uint32_t w[4] = {raw.x, raw.y, raw.z, raw.w};
-  if constexpr (CHEAP) {      // (timing experiments only: 16 instead of 52 operations, no dependent chains)
-#pragma unroll
-    for (int i = 0; i < 16; ++i) out[i] = __builtin_bit_cast(v2h, w[i & 3]) * scale2;
-    return;
-  }
-  const v2h k1024 = {(half_t)1024.0f, (half_t)1024.0f};
-  const v2h k16th = {(half_t)0.0625f, (half_t)0.0625f};
-  const v2h k64 = {(half_t)64.0f, (half_t)64.0f};
-  const uint32_t magic = 0x64006400u;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const uint32_t x = w[i], y = w[i] >> 8;
-    uint32_t h0 = and_or(x, 0x000f000fu, magic);  // {1024+e0, 1024+e4}
-    uint32_t h1 = and_or(x, 0x00f000f0u, magic);  // {1024+16 e1, 1024+16 e5}
-    uint32_t h2 = and_or(y, 0x000f000fu, magic);  // e2, e6
-    uint32_t h3 = and_or(y, 0x00f000f0u, magic);  // e3, e7
-    v2h u0 = __builtin_bit_cast(v2h, h0) - k1024;
-    v2h u1 = __builtin_elementwise_fma(__builtin_bit_cast(v2h, h1), k16th, -k64);
-    v2h u2 = __builtin_bit_cast(v2h, h2) - k1024;
-    v2h u3 = __builtin_elementwise_fma(__builtin_bit_cast(v2h, h3), k16th, -k64);
-    out[i * 4 + 0] = __builtin_elementwise_fma(u0, scale2, c2);
-    out[i * 4 + 1] = __builtin_elementwise_fma(u1, scale2, c2);
-    out[i * 4 + 2] = __builtin_elementwise_fma(u2, scale2, c2);
-    out[i * 4 + 3] = __builtin_elementwise_fma(u3, scale2, c2);
-  }
-}
-
+// (and_or / kv4_dequant16: kv4_dequant.h, shared with the prefill attention over the pages)
 // KV8 (per-tensor int8): out[i] = {h(s*f32(b_2i)), h(s*f32(b_2i+1))} for the 16 bytes of `raw`, natural order
 // (common/decoderMaskedMultiheadAttentionUtils.h:2086-2093: f32 multiply, then one rounding to fp16)
 __device__ __forceinline__ void kv8_dequant16(const uint4 raw, float s, v2h out[8]) {
@@ -1253,12 +1219,12 @@ extern "C" int omni_compute_padding_offsets(void* out_i32, const void* cu_seqlen
   return omni_launch_status();
 }
 
-extern "C" int omni_kv4_prefill_write(void* qkv_f16, const void* seq_lens_i32,
-                                      const void* padding_offsets_i32, const void* kv_pointers_i64,
-                                      int tokens, int batch, int max_blocks, int num_heads,
-                                      int num_kv_heads, int head_dim, int max_seq_len,
-                                      int tokens_per_block, const void* rope_cos_sin_f32,
-                                      int rope_max_pos, int max_position_embeddings, void* stream) {
+static int kv4_prefill_write_dense(void* qkv_f16, const void* seq_lens_i32, const void* past_lens_i32,
+                                   const void* padding_offsets_i32, const void* kv_pointers_i64,
+                                   int tokens, int batch, int max_blocks, int num_heads,
+                                   int num_kv_heads, int head_dim, int max_seq_len,
+                                   int tokens_per_block, const void* rope_cos_sin_f32,
+                                   int rope_max_pos, int max_position_embeddings, void* stream) {
   if (!qkv_f16 || !seq_lens_i32 || !padding_offsets_i32 || !kv_pointers_i64 || !rope_cos_sin_f32)
     return OMNI_EINVAL;
   if (head_dim != DH || tokens < 0 || batch < 1 || num_heads < 1 || num_kv_heads < 1 ||
@@ -1273,8 +1239,36 @@ extern "C" int omni_kv4_prefill_write(void* qkv_f16, const void* seq_lens_i32,
                      (const int64_t*)kv_pointers_i64, tokens, max_blocks, num_heads, num_kv_heads,
                      max_seq_len, make_layout(tokens_per_block, num_kv_heads),
                      (const float*)rope_cos_sin_f32, rope_max_pos, max_position_embeddings, FgArgs{},
-                     (const float*)nullptr);
+                     (const float*)nullptr, (const int*)past_lens_i32);
   return omni_launch_status();
+}
+
+extern "C" int omni_kv4_prefill_write(void* qkv_f16, const void* seq_lens_i32,
+                                      const void* padding_offsets_i32, const void* kv_pointers_i64,
+                                      int tokens, int batch, int max_blocks, int num_heads,
+                                      int num_kv_heads, int head_dim, int max_seq_len,
+                                      int tokens_per_block, const void* rope_cos_sin_f32,
+                                      int rope_max_pos, int max_position_embeddings, void* stream) {
+  return kv4_prefill_write_dense(qkv_f16, seq_lens_i32, nullptr, padding_offsets_i32, kv_pointers_i64, tokens, batch,
+                                 max_blocks, num_heads, num_kv_heads, head_dim, max_seq_len, tokens_per_block,
+                                 rope_cos_sin_f32, rope_max_pos, max_position_embeddings, stream);
+}
+
+// The same writer for tokens that continue a sequence (chunked prefill, multi-turn): token i of sequence b is position
+// past_lens[b] + i.  Dense KV4 with zero points only.
+extern "C" int omni_kv4_prefill_write_at(void* qkv_f16, const void* seq_lens_i32, const void* past_lens_i32,
+                                         const void* padding_offsets_i32, const void* kv_pointers_i64,
+                                         int tokens, int batch, int max_blocks, int num_heads,
+                                         int num_kv_heads, int head_dim, int max_seq_len,
+                                         int tokens_per_block, const void* rope_cos_sin_f32,
+                                         int rope_max_pos, int max_position_embeddings, void* stream) {
+  if (!past_lens_i32) return OMNI_EINVAL;
+  // (the past lengths live on the device: the table must cover max(past + len), which the host side that knows them checks --
+  //  fused_ext.kv4_prefill_write_at; here only what the arguments show: the table covers the call's own tokens)
+  if (rope_max_pos < max_seq_len) return OMNI_EINVAL;
+  return kv4_prefill_write_dense(qkv_f16, seq_lens_i32, past_lens_i32, padding_offsets_i32, kv_pointers_i64, tokens, batch,
+                                 max_blocks, num_heads, num_kv_heads, head_dim, max_seq_len, tokens_per_block,
+                                 rope_cos_sin_f32, rope_max_pos, max_position_embeddings, stream);
 }
 
 static int fill_fg(FgArgs* fg, const void* streaming_kv_pointers_i64, const void* retrieval_head_flags_i32,
@@ -1328,13 +1322,13 @@ static int prefill_write_fg_common(
                        (half_t*)qkv_f16, (const int*)seq_lens_i32, (const int*)padding_offsets_i32,
                        (const int64_t*)retrieval_kv_pointers_i64, tokens, retrieval_blocks, num_heads, num_kv_heads,
                        max_seq_len, make_layout(tokens_per_block, num_kv_heads),
-                       (const float*)rope_cos_sin_f32, rope_max_pos, max_position_embeddings, fg, kv_oq);
+                       (const float*)rope_cos_sin_f32, rope_max_pos, max_position_embeddings, fg, kv_oq, (const int*)nullptr);
   else
     hipLaunchKernelGGL(kv4_prefill_write_kernel<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream,
                        (half_t*)qkv_f16, (const int*)seq_lens_i32, (const int*)padding_offsets_i32,
                        (const int64_t*)retrieval_kv_pointers_i64, tokens, retrieval_blocks, num_heads, num_kv_heads,
                        max_seq_len, make_layout(tokens_per_block, num_kv_heads),
-                       (const float*)rope_cos_sin_f32, rope_max_pos, max_position_embeddings, fg, kv_oq);
+                       (const float*)rope_cos_sin_f32, rope_max_pos, max_position_embeddings, fg, kv_oq, (const int*)nullptr);
   return omni_launch_status();
 }
 

@@ -595,14 +595,20 @@ class DecodeRunner:
             self.tokens.copy_(torch.argmax(logits, dim=-1))
 
     # ---- prefill (context stage) ---------------------------------------------------------------------------
-    def prefill(self, prompt_len=None, tokens=None):
+    def prefill(self, prompt_len=None, tokens=None, chunk=None):
         """One context-stage pass over `prompt_len` tokens per sequence in the order of the reference's decoder
         layer at prefill shape (llama_w4a8_unpad.py:406-438 with M = B * prompt_len; ctx_update_kv.py:96-135;
         ctx_attn_func.py:68-73): norm+quant -> qkv GEMM -> RoPE in place + KV4 page write -> varlen causal
         attention -> quant -> o GEMM -> add -> norm+quant -> gate_up GEMM -> silu*mul -> quant -> down GEMM -> add.
         Fills the KV pools for positions [0, prompt_len) and leaves the first generated token in self.tokens
         (self.lengths = prompt_len), i.e. the qserve_benchmark.py protocol's prefill step.  Eager launches.
-        `tokens`: the B * prompt_len prompt token ids, sequence after sequence (default: random ids)."""
+        `tokens`: the B * prompt_len prompt token ids, sequence after sequence (default: random ids).
+        `chunk`: chunked prefill -- the prompt goes through in ceil(prompt_len / chunk) extend() calls of at most `chunk` tokens
+        per sequence, with activation buffers of B * chunk rows instead of B * prompt_len.  Later chunks see the earlier ones
+        through the KV4 pages, as every decode step does, so the result is close to but not bit-identical with the
+        whole-prompt pass; chunk >= prompt_len is the whole-prompt pass."""
+        if chunk is not None:
+            return self._prefill_chunked(prompt_len, tokens, int(chunk))
         import omniserve_backend.fused_attention_fine_grained_dense as fgd
         from .backend.prefill_attn import flash_attn_varlen_func
         c, B, dev = self.cfg, self.B, self.device
@@ -672,6 +678,100 @@ class DecodeRunner:
         logits = torch.matmul(self.normed, self.lm_head.t())
         self.tokens.copy_(torch.argmax(logits, dim=-1))
         self.lengths.fill_(L)
+
+    def _prefill_chunked(self, prompt_len, tokens, chunk):
+        c, B = self.cfg, self.B
+        L = int(prompt_len if prompt_len is not None else self.lengths[0].item())
+        if chunk < 1:
+            raise ValueError("chunk must be at least one token")
+        if L < 1 or L + 1 > self.max_context:
+            raise ValueError("prompt length does not fit the runner's KV pools")
+        if tokens is None:
+            tokens = torch.randint(0, c.vocab, (B * L,), device=self.device, generator=self.gen)
+        elif tokens.numel() != B * L:
+            raise ValueError("prefill expects %d prompt tokens, got %d" % (B * L, tokens.numel()))
+        tokens = tokens.view(B, L)
+        self.lengths.zero_()
+        for s in range(0, L, chunk):
+            self.extend(min(chunk, L - s), tokens[:, s:s + chunk].reshape(-1))
+
+    def extend(self, new_len, tokens=None):
+        """Append `new_len` tokens per sequence behind the self.lengths tokens (which may differ per sequence) already in the
+        KV pools: chunked prefill, a further turn of a conversation, the suffix behind a shared prefix.  The layer sequence of
+        prefill() with the writer at an offset (fused_ext.kv4_prefill_write_at) and the attention that continues from the pages
+        (fused_ext.prefill_attention_paged_kv4: quantised past, fresh chunk) in place of its writer / attention pair.  Updates
+        self.lengths and leaves the next token in self.tokens.  `tokens`: B * new_len ids, sequence after sequence (default:
+        random ids).  With nothing in the pools yet (every length 0) this is prefill(new_len, tokens) itself."""
+        from .backend.fused_attention_fine_grained_dense import compute_padding_offsets
+        c, B, dev = self.cfg, self.B, self.device
+        n = int(new_len)
+        past_max = int(self.lengths.max().item())
+        if n < 1:
+            raise ValueError("extend needs at least one new token per sequence")
+        if past_max + n + 1 > self.max_context:
+            raise ValueError("lengths + new_len does not fit the runner's KV pools")
+        if past_max == 0:
+            return self.prefill(n, tokens)
+        T = B * n
+        hq, hk, d = self.hl, self.kl, c.head_dim
+        f16, i8 = torch.float16, torch.int8
+        buf = getattr(self, "_prefill_bufs", None)
+        if buf is None or buf["T"] < T:      # (a chunked prefill's first chunk sized them: the later ones are no longer)
+            buf = dict(T=T, x=torch.empty((T, c.hidden), dtype=f16, device=dev),
+                       qh=torch.empty((T, c.hidden), dtype=i8, device=dev),
+                       qi=torch.empty((T, self.il), dtype=i8, device=dev),
+                       qa=torch.empty((T, hq * d), dtype=i8, device=dev),
+                       qkv=torch.empty((T, (hq + 2 * hk) * d), dtype=f16, device=dev),
+                       proj=torch.empty((T, c.hidden), dtype=f16, device=dev),
+                       gu=torch.empty((T, 2 * self.il), dtype=f16, device=dev),
+                       s1=torch.empty((T,), dtype=f16, device=dev), m1=torch.empty((T,), dtype=f16, device=dev),
+                       s2=torch.empty((T,), dtype=f16, device=dev), m2=torch.empty((T,), dtype=f16, device=dev))
+            self._prefill_bufs = buf
+        x, qh, qi, qa, qkv, proj, gu = (buf[name][:T] for name in ("x", "qh", "qi", "qa", "qkv", "proj", "gu"))
+        sB, mB, sA, mA = (buf[name][:T] for name in ("s1", "m1", "s2", "m2"))
+        if tokens is None:
+            tokens = torch.randint(0, c.vocab, (T,), device=dev, generator=self.gen)
+        elif tokens.numel() != T:
+            raise ValueError("extend expects %d tokens, got %d" % (T, tokens.numel()))
+        torch.index_select(self.embed, 0, tokens.reshape(-1), out=x)
+        lens = torch.full((B,), n, dtype=torch.int32, device=dev)
+        past = self.lengths.clone()
+        cu = torch.arange(0, B + 1, dtype=torch.int32, device=dev) * n
+        pad = compute_padding_offsets(cu, n, T)
+        q = qkv[:, : hq * d].view(T, hq, d)
+        k = qkv[:, hq * d:(hq + hk) * d].view(T, hk, d)
+        v = qkv[:, (hq + hk) * d:].view(T, hk, d)
+        per_chn = c.group_size == -1
+        if not per_chn:
+            mA = mB = None      # g128: no activation sums (see _eager_step_body)
+        for li, Ly in enumerate(self.layers):
+            if li == 0 and per_chn:
+                layernorm_ops.rms_norm_general_fuse_sum(qh, x, Ly["ln1"], mB, sB, c.eps, True)
+            elif li == 0:
+                layernorm_ops.rms_norm_general(qh, x, Ly["ln1"], sB, c.eps, True)
+            else:
+                fused_ext.add_rms_norm_general_fuse_sum(qh, x, proj, Ly["ln1"], mB, sB, c.eps)
+            Ly["qkv"].forward(qh, sB, mB, qkv)
+            fused_ext.kv4_prefill_write_at(qkv, lens, past, pad, self.block_tables[li], hq, hk, n, self.tpb, past_max + n,
+                                           c.rope_theta, 1.0, 1 << 20)
+            attn = fused_ext.prefill_attention_paged_kv4(q, k, v, cu, past, self.block_tables[li], self.tpb, n)
+            if per_chn:
+                fused_kernels.invoke_quant_fuse_sum(qa, attn.view(T, hq * d), mA, sA)
+            else:
+                fused_kernels.invoke_quant(qa, attn.view(T, hq * d), sA)
+            Ly["o"].forward(qa, sA, mA, proj)
+            self._all_reduce(proj)
+            fused_ext.add_rms_norm_general_fuse_sum(qh, x, proj, Ly["ln2"], mB, sB, c.eps)
+            Ly["gate_up"].forward(qh, sB, mB, gu)
+            fused_ext.silu_mul_quant_fuse_sum(qi, gu, mA, sA)
+            Ly["down"].forward(qi, sA, mA, proj)
+            self._all_reduce(proj)
+        x.add_(proj)
+        self.x.copy_(x.view(B, n, c.hidden)[:, n - 1])
+        layernorm_ops.rms_norm(self.normed, self.x, self.final_norm, c.eps, False)
+        logits = torch.matmul(self.normed, self.lm_head.t())
+        self.tokens.copy_(torch.argmax(logits, dim=-1))
+        self.lengths.add_(n)
 
     def _all_reduce(self, buf):
         if self.tp_size > 1:
