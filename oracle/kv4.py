@@ -179,7 +179,7 @@ def prefill_write(qkv_h, seq_lens, k_cache: PagedKV4, v_cache: PagedKV4, k_table
 
 
 def decode_attention(q_h, k_h, v_h, lengths, k_cache: PagedKV4, v_cache: PagedKV4, k_table, v_table,
-                     rope_base, emulate_fp16: bool = False):
+                     rope_base, emulate_fp16: bool = False, out_f32=None):
     """single_query_attention (pure dense, KV4 + zeros, neox RoPE, Dh = rotary dim).
 
     q fp16 [B,Hq,D], k,v fp16 [B,Hkv,D]; lengths[b] = context length INCLUDING
@@ -192,7 +192,8 @@ def decode_attention(q_h, k_h, v_h, lengths, k_cache: PagedKV4, v_cache: PagedKV
     does the history q.k products in fp16 pairs as the reference does
     (Template.hpp:451-467,1794-1845); emulate_fp16=False is the f32 reference
     the HIP kernel is compared against (rtol 1e-3).
-    Returns out fp16 [B,Hq,D].
+    Returns out fp16 [B,Hq,D]; out_f32 (optional float32 [B,Hq,D]) receives the same values before that last
+    rounding (tests that measure the f32 arithmetic alone, without fp16 rounding-boundary flips).
     """
     q_h = np.asarray(q_h, F16)
     B, Hq, D = q_h.shape
@@ -225,6 +226,8 @@ def decode_attention(q_h, k_h, v_h, lengths, k_cache: PagedKV4, v_cache: PagedKV
                 vals = np.concatenate([Vc, vr[hk][None, :].astype(F32)], axis=0)
                 o = (p[:, None].astype(np.float64) * vals.astype(np.float64)).sum(axis=0)
                 out[b, hq] = o.astype(F32).astype(F16)
+                if out_f32 is not None:
+                    out_f32[b, hq] = o.astype(F32)
             # append current token (quantized) -- after the reads above
             k_cache.write_token(int(k_table[b][tlen // k_cache.TPB]), tlen % k_cache.TPB, hk, kr[hk])
             v_cache.write_token(int(v_table[b][tlen // v_cache.TPB]), tlen % v_cache.TPB, hk, vr[hk])
