@@ -21,116 +21,25 @@
 // ds_read_b64_tr_b16.  Probabilities never leave registers; row statistics reduce over the 4 lanes that share a
 // query row.  Tiles that need no masking skip the per-element predicate (workgroup-uniform).  With q_tiles > 0 the
 // grid is 1-D and XCD-aware (prefill_map_block: the q heads of a kv head share an XCD's L2; dense work balanced over XCDs).
-#include "common.h"
+#include "attn_prefill_tile.h"
 
 namespace omni {
 
-constexpr int PDH = 128;
-constexpr int PKT = 64;               // keys per tile
-#ifndef OMNI_PREFILL_PQB
-#define OMNI_PREFILL_PQB 1
-#endif
-constexpr int PQB = OMNI_PREFILL_PQB;   // 16-row query blocks per wave
-#ifndef OMNI_PREFILL_MFMA32
-#define OMNI_PREFILL_MFMA32 0          // default kernel: 0 = 16-row form, 1 = 32-row form (prefill_attn32_kernel); omni_prefill_set_variant overrides
-#endif
-#ifndef OMNI_PREFILL_ABLATE_DMA
-#define OMNI_PREFILL_ABLATE_DMA 0     // timing experiment (wrong results): no tile DMA after the first tile
-#endif
+// 16-row query blocks per wave in prefill_attn_kernel.  Fixed at 1 (the launch bounds, PQROWS and the ping-pong form assume it);
+// the kernel keeps its [PQB] dimension and the one-trip `for (j < PQB)` loops around its softmax and its store because they
+// shape its code: with the dimension dropped (and nothing else changed) hipcc lays out the two softmax paths differently and
+// the kernel grows from 2081 to 2103 lines of assembly.
+constexpr int PQB = 1;
 
-#ifndef OMNI_PREFILL_WAVES
-#define OMNI_PREFILL_WAVES (8 / OMNI_PREFILL_PQB)
-#endif
-constexpr int PWAVES = OMNI_PREFILL_WAVES;         // 8 waves x 16 rows: ~120 VGPRs per wave, 4 waves per SIMD hide the softmax VALU work
-constexpr int PPT = (PKT * 16) / (64 * PWAVES);   // 1-KiB LDS-DMA pieces of a K (or V) tile per wave
-constexpr int PQROWS = 16 * PQB * PWAVES;   // 128 query rows per workgroup
-constexpr int PKROW = 256;            // bytes per key row of the K tile (swizzled slots)
-constexpr int PVROW = 256;            // bytes per key row of the V tile (swizzled slots, see the kernel)
-constexpr int PKTILE = PKT * PKROW, PVTILE = PKT * PVROW;
-typedef __fp16 pv4hp __attribute__((__vector_size__(4 * sizeof(__fp16))));
-
-__device__ __forceinline__ int xor_nohoist(int a, int uniform_b) {
-  int r;
-  asm volatile("v_xor_b32 %0, %2, %1" : "=v"(r) : "v"(a), "s"(uniform_b));
-  return r;
-}
-
-struct PrefillArgs {
-  const half_t* q; const half_t* k; const half_t* v; half_t* out;
-  int64_t q_stride, k_stride, v_stride;     // elements between consecutive tokens
-  const int* cu_q; const int* cu_k;
-  const int* head_mask_type;                 // [Hq] or null (all dense)
-  const int* streaming_info;                 // [2*Hq] (sink, local) or null
-  int num_heads, num_kv_heads;
-  int causal;
-  int q_tiles;                               // > 0: 1-D grid, XCD-aware order (prefill_map_block)
-  int xcd_split;                             // 1-D grid: XCDs that share the query tiles of one kv head (1, 2, 4 or 8)
-  int gran_log2;                             // granularity of (sink, local): 0 tokens (token_streaming_attn_func), 7 blocks of 128
-};                                           // tokens (block_streaming_attn_func): see first_local_key below
-
-// Streaming heads see the keys  key < sink << g  and  key >= first_local_key(qpos): the first key of the local window of the
-// query at (bottom-right aligned) position qpos.  g = 0: qpos - local + 1 (the last `local` tokens, itself included); g = 7:
-// the first token of block (qpos >> 7) - local + 1 (the query's own 128-token block and the local - 1 blocks before it).
-__device__ __forceinline__ int first_local_key(int qpos, int local, int g) { return ((qpos >> g) - local + 1) * (1 << g); }
-// A (sink, local) entry as the kernels use it: clamped to [0, (len_k >> g) + 1] units of 1 << g tokens, once per workgroup and
-// before any shift or multiply.  (len_k >> g) + 1 units already cover every key of the sequence -- sink: ((len_k >> g) + 1) << g
-// > len_k; local: qpos <= len_k - 1, so first_local_key <= 0 -- hence the clamp changes no element predicate and no tile
-// predicate (skipped / full / win_lo all use the clamped pair), and it keeps sink << g and first_local_key inside int32 for
-// every int32 entry: |first_local_key| <= len_q + len_k + (2 << g).  Unclamped, the block form wrapped from 1 << 24 on ("everything"
-// put the window behind the query: rows of zeros), the token form for queries at negative positions (len_q > len_k).  Negative
-// entries count as 0: no sink; no local key at or before the query.
-__device__ __forceinline__ int window_units(int entry, int len_k, int g) { return min(max(entry, 0), (len_k >> g) + 1); }
-
-// 1-D grid: workgroups are dealt round-robin to the 8 XCDs (private L2s; the dispatch is static: workgroup w runs on XCD
-// w % 8 whatever the others are doing).  All q heads of a kv head share an XCD's L2, so a K/V tile is fetched from the
-// fabric once per XCD that works on the head; the query tiles of a kv head are spread over W = xcd_split XCDs (tile t of
-// part t % W) so that every XCD gets the same amount of DENSE work when some kv heads are streaming heads (LServe: a dense
-// head costs O(L^2), a streaming head O(L * window); with whole kv heads pinned to XCDs the XCDs that drew streaming heads
-// idle for most of the launch).  kv heads are taken dense-first: sorted position pos, part j -> XCD (pos * W + j) % 8.
-// Returns false for the padding workgroups of a part that has fewer tiles.
-__device__ __forceinline__ bool prefill_map_block(const PrefillArgs& p, int& b, int& h, int& qt) {
-  const int W = p.xcd_split, Hk = p.num_kv_heads, G = p.num_heads / Hk;
-  const int P = (Hk * W) >> 3;                       // (kv head, part) pairs per XCD
-  const int R = (p.q_tiles + W - 1) / W;             // tile rows of a part
-  const int wid = blockIdx.x, xcd = wid & 7;
-  int slot = wid >> 3;
-  const int u = slot % G; slot /= G;
-  const int i = slot % P; slot /= P;
-  const int r = slot % R;
-  b = slot / R;
-  const int idx = xcd + 8 * i, pos = idx / W, j = idx - pos * W;
-  qt = p.q_tiles - 1 - (r * W + j);                  // long (late) query tiles first
-  int kvh = pos;
-  if (p.head_mask_type != nullptr) {                 // pos-th kv head in dense-first order (Hk scalar loads, once)
-    int nd = 0;
-    for (int t = 0; t < Hk; ++t) nd += p.head_mask_type[t * G] >= 0;
-    const bool want_dense = pos < nd;
-    int left = want_dense ? pos : pos - nd;
-    kvh = 0;
-    for (int t = 0; t < Hk; ++t) {
-      const bool dense = p.head_mask_type[t * G] >= 0;
-      if (dense == want_dense) {
-        if (left == 0) { kvh = t; break; }
-        --left;
-      }
-    }
-  }
-  h = kvh * G + u;
-  return qt >= 0;
-}
-
-#ifndef OMNI_PREFILL_MIN_BLOCKS
-#define OMNI_PREFILL_MIN_BLOCKS 2
-#endif
-__global__ __launch_bounds__(64 * PWAVES, OMNI_PREFILL_MIN_BLOCKS) __attribute__((amdgpu_waves_per_eu(4 / PQB, 4 / PQB), amdgpu_num_vgpr(512 / (4 / PQB))))   // 128 VGPRs (PQB = 1) or 256 (PQB = 2)
+__global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(4, 4), amdgpu_num_vgpr(128)))
 void prefill_attn_kernel(PrefillArgs p) {
   // four separate LDS objects and a loop body instantiated per buffer parity (static indices): with one array and a
   // runtime buffer index the compiler cannot tell the DMA target from the tile being read and puts vmcnt(0) -- the
   // whole flight time of the next tile -- in front of the first LDS read of every iteration
-  __shared__ __attribute__((aligned(16))) uint8_t ktile0[PKTILE];
-  __shared__ __attribute__((aligned(16))) uint8_t ktile1[PKTILE];
-  __shared__ __attribute__((aligned(16))) uint8_t vtile0[PVTILE];
-  __shared__ __attribute__((aligned(16))) uint8_t vtile1[PVTILE];
+  __shared__ __attribute__((aligned(16))) uint8_t ktile0[PTILE];
+  __shared__ __attribute__((aligned(16))) uint8_t ktile1[PTILE];
+  __shared__ __attribute__((aligned(16))) uint8_t vtile0[PTILE];
+  __shared__ __attribute__((aligned(16))) uint8_t vtile1[PTILE];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int l15 = lane & 15, l4 = lane >> 4;
   int b = blockIdx.z, h = blockIdx.y, qt = gridDim.x - 1 - blockIdx.x;   // long (late) query tiles are scheduled first
@@ -148,18 +57,10 @@ void prefill_attn_kernel(PrefillArgs p) {
   const int sink = streaming ? window_units(p.streaming_info[2 * h], len_k, gl) << gl : 0;      // in tokens
   const int local = streaming ? window_units(p.streaming_info[2 * h + 1], len_k, gl) : 0;       // in units of 1 << gl tokens
   const float scale2 = 0.08838834764831845f * 1.4426950408889634f;   // log2(e)/sqrt(128): scores in the exp2 domain
-
-  // B operand of S^T = K Q^T: Q[row][32s + 8*l4 + (0..7)] for the wave's two row blocks
   int qrow[PQB];
   v8h qb[PQB][4];
-#pragma unroll
-  for (int j = 0; j < PQB; ++j) {
-    qrow[j] = q0 + 16 * j + l15;
-    const int qr_c = qrow[j] < len_q ? qrow[j] : (len_q - 1);
-    const half_t* qp = p.q + (size_t)(q_begin + qr_c) * p.q_stride + (size_t)h * PDH + 8 * l4;
-#pragma unroll
-    for (int s = 0; s < 4; ++s) qb[j][s] = *reinterpret_cast<const v8h*>(qp + 32 * s);
-  }
+  qrow[0] = q0 + l15;
+  load_q16(p.q, p.q_stride, q_begin, qrow[0], len_q, h, l4, qb[0]);
   v4f oacc[PQB][8];
   float m_run[PQB], l_run[PQB];
 #pragma unroll
@@ -186,19 +87,18 @@ void prefill_attn_kernel(PrefillArgs p) {
   const uint8_t* kbase = reinterpret_cast<const uint8_t*>(p.k + (size_t)k_begin * p.k_stride + (size_t)hk * PDH);
   const uint8_t* vbase = reinterpret_cast<const uint8_t*>(p.v + (size_t)k_begin * p.v_stride + (size_t)hk * PDH);
   const uint32_t kstride_b = (uint32_t)(p.k_stride * 2), vstride_b = (uint32_t)(p.v_stride * 2);   // host: < 2^32
-#define PREFILL_DMA16(src_, dst_) lds_dma16((src_), (dst_))
 #define PREFILL_DMA_TILE(kb_, kt_, vt_)                                                                           \
   do {                                                                                                            \
     int ln_ = lane;                                                                                               \
-    asm volatile("" : "+v"(ln_));   /* opaque per tile: the per-piece lane constants must not be hoisted */         \
-    const int ss_ = ln_ & 15, lr_ = ln_ >> 4;                                                                      \
+    asm volatile("" : "+v"(ln_));   /* opaque per tile: the per-piece lane constants must not be hoisted */       \
+    const int ss_ = ln_ & 15, lr_ = ln_ >> 4;                                                                     \
     _Pragma("unroll") for (int i_ = 0; i_ < PPT; ++i_) {                                                          \
       const int row_ = 4 * PPT * wave + 4 * i_ + lr_;                                                             \
       const uint32_t kr_ = (uint32_t)((kb_) + row_ < len_k ? (kb_) + row_ : (len_k - 1));                         \
-      PREFILL_DMA16(kbase + ((uint64_t)kr_ * kstride_b + (uint32_t)((ss_ ^ (row_ & 15)) << 4)),                   \
-                    (kt_) + (4 * PPT * wave + 4 * i_) * PKROW);                                                   \
-      PREFILL_DMA16(vbase + ((uint64_t)kr_ * vstride_b + (uint32_t)((ss_ ^ (2 * (row_ & 7))) << 4)),              \
-                    (vt_) + (4 * PPT * wave + 4 * i_) * PVROW);                                                   \
+      lds_dma16(kbase + ((uint64_t)kr_ * kstride_b + (uint32_t)((ss_ ^ (row_ & 15)) << 4)),                       \
+                (kt_) + (4 * PPT * wave + 4 * i_) * PROW);                                                        \
+      lds_dma16(vbase + ((uint64_t)kr_ * vstride_b + (uint32_t)((ss_ ^ (2 * (row_ & 7))) << 4)),                  \
+                (vt_) + (4 * PPT * wave + 4 * i_) * PROW);                                                        \
     }                                                                                                             \
   } while (0)
   auto next_tile = [&](int kb) {     // first tile >= kb that is not skipped (or >= k_hi)
@@ -206,10 +106,7 @@ void prefill_attn_kernel(PrefillArgs p) {
     return kb;
   };
 
-  // V^T operand: row 4*l4 + l15/4 (+16, +32, +48 by immediates), 8 B at logical offset 32c + 8*(l15&3); the physical
-  // 32-B block of logical block c is c ^ (row & 7)
-  const int trow = 4 * l4 + (l15 >> 2);
-  const int tr_a0 = (trow * PVROW + (l15 & 3) * 8) | ((trow & 7) << 5);   // address of logical block c: tr_a0 ^ (c << 5)
+  const int tr_a0 = pv16_lane_addr(l15, l4);
   int kb = next_tile(0);
   if (kb < k_hi) PREFILL_DMA_TILE(kb, ktile0, vtile0);
   __syncthreads();     // (carries the vmcnt(0) of the DMA pieces)
@@ -218,36 +115,17 @@ void prefill_attn_kernel(PrefillArgs p) {
     const int kb_next = next_tile(kb + PKT);
     const uint8_t* kt = B ? ktile1 : ktile0;
     const uint8_t* vt = B ? vtile1 : vtile0;
-    // ---- S^T tile: 4 blocks of 16 keys x 2 query blocks ---------------------------------------------------
     // (MFMA phases run at raised priority: a wave that has matrix work ready goes ahead of the waves in their softmax)
     __builtin_amdgcn_s_setprio(1);
     v4f st[PQB][4];
-#pragma unroll
-    for (int j = 0; j < PQB; ++j)
-#pragma unroll
-      for (int u = 0; u < 4; ++u) st[j][u] = (v4f){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int key = 16 * u + l15;
-#pragma unroll
-      for (int s = 0; s < 4; ++s) {
-        const v8h a = *reinterpret_cast<const v8h*>(kt + key * PKROW + (((4 * s + l4) ^ l15) << 4));
-#pragma unroll
-        for (int j = 0; j < PQB; ++j) st[j][u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, qb[j][s], st[j][u], 0, 0, 0);
-      }
-    }
-    // st[j][u][r] = K[kb + 16u + 4*l4 + r] . Q[qrow[j]]
+    stage_s16(kt, qb[0], l15, l4, st[0]);
     // The next tile starts its trip global -> LDS (other buffer: every wave left it at the previous barrier) only
     // now: while a DMA is in flight hipcc waits lgkmcnt(0) in front of every consumer of a ds_read (it books the DMA
     // as a second kind of LDS event), which would serialise the 16 operand reads above against their MFMAs; the
     // softmax and the P.V phase below (whose reads are batched by hand) cover the flight time.
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_setprio(0);
-#if OMNI_PREFILL_ABLATE_DMA == 2     // timing experiment (wrong results): every tile re-fetches the first tile (L2-hot)
-    if (kb_next < k_hi) PREFILL_DMA_TILE(0, B ? ktile0 : ktile1, B ? vtile0 : vtile1);
-#elif !OMNI_PREFILL_ABLATE_DMA
     if (kb_next < k_hi) PREFILL_DMA_TILE(kb_next, B ? ktile0 : ktile1, B ? vtile0 : vtile1);
-#endif
     __builtin_amdgcn_sched_barrier(0);
     // does any (row, key) pair of this workgroup's tile need the mask?  (workgroup-uniform)
     bool full = (kb + PKT <= len_k) && (q_first + PQROWS <= len_q);
@@ -305,40 +183,8 @@ void prefill_attn_kernel(PrefillArgs p) {
       }
       m_run[j] = m_new;
     }
-    // ---- O^T += V^T P^T ------------------------------------------------------------------------------------------
-    // 16 steps (kk, c), each = two transposed reads (the A operand V^T) + one MFMA.  The schedule is pinned with
-    // sched_group_barrier: the reads run three steps ahead of the MFMAs (three operand quads in flight, counted
-    // lgkmcnt waits).  Left alone the compiler reuses ONE operand quad: read -> lgkmcnt(0) -> MFMA sixteen times per
-    // tile (PMC: 44 % of the wave cycles parked on counters).
     __builtin_amdgcn_s_setprio(1);
-    {
-      v8h a16[16];
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        const int kk = i >> 3, c = i & 7;
-        // the xor is recomputed per step (volatile asm): hoisted out of the tile loop the eight addresses cost eight
-        // VGPRs, which pushed the kernel over the 128 that four waves per SIMD allow
-        const uint8_t* src = vt + (32 * kk) * PVROW + (tr_a0 ^ (c << 5));
-        const pv4hp lo = __builtin_amdgcn_ds_read_tr16_b64_v4f16(
-            (__attribute__((address_space(3))) pv4hp*)(__attribute__((address_space(3))) void*)(src));
-        const pv4hp hi = __builtin_amdgcn_ds_read_tr16_b64_v4f16(
-            (__attribute__((address_space(3))) pv4hp*)(__attribute__((address_space(3))) void*)(src + 16 * PVROW));
-        a16[i] = (v8h){(half_t)lo[0], (half_t)lo[1], (half_t)lo[2], (half_t)lo[3],
-                       (half_t)hi[0], (half_t)hi[1], (half_t)hi[2], (half_t)hi[3]};
-      }
-#pragma unroll
-      for (int i = 0; i < 16; ++i)
-#pragma unroll
-        for (int j = 0; j < PQB; ++j)
-          oacc[j][i & 7] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a16[i], pb[j][i >> 3], oacc[j][i & 7], 0, 0, 0);
-      __builtin_amdgcn_sched_group_barrier(0x100, 6, 0);          // DS reads of steps 0..2
-#pragma unroll
-      for (int i = 0; i < 13; ++i) {
-        __builtin_amdgcn_sched_group_barrier(0x008, PQB, 0);      // MFMA of step i
-        __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);        // DS reads of step i + 3
-      }
-      __builtin_amdgcn_sched_group_barrier(0x008, 3 * PQB, 0);
-    }
+    stage_pv16(vt, tr_a0, pb[0], oacc[0]);
     __builtin_amdgcn_s_setprio(0);
     // ---- the next tile has landed (vmcnt(0) of this wave's DMA pieces rides in the barrier) ----------------------
     __syncthreads();
@@ -349,22 +195,8 @@ void prefill_attn_kernel(PrefillArgs p) {
     if (kb >= k_hi) break;
     tile_step(IntTag<1>{});
   }
-  // ---- finish: row sum over the 4 lanes of a query row, normalise, store ------------------------------------
 #pragma unroll
-  for (int j = 0; j < PQB; ++j) {
-    float l = l_run[j];
-    l = rows4_sum(l);
-    if (qrow[j] >= len_q) continue;
-    const float inv = l > 0.0f ? 1.0f / l : 0.0f;
-    half_t* op = p.out + ((size_t)(q_begin + qrow[j]) * p.num_heads + h) * PDH + 4 * l4;
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-      typedef _Float16 v4h_t __attribute__((ext_vector_type(4)));
-      const v4h_t o = {(half_t)(oacc[j][c][0] * inv), (half_t)(oacc[j][c][1] * inv), (half_t)(oacc[j][c][2] * inv),
-                       (half_t)(oacc[j][c][3] * inv)};
-      *reinterpret_cast<v4h_t*>(op + c * 16) = o;
-    }
-  }
+  for (int j = 0; j < PQB; ++j) store_rows16(p.out, q_begin, qrow[j], len_q, p.num_heads, h, l4, l_run[j], oacc[j]);
 }
 
 #undef PREFILL_DMA_TILE
@@ -383,28 +215,27 @@ void prefill_attn_kernel(PrefillArgs p) {
 // K(i)'s -- were last read in segment 2i) and are waited for (vmcnt(0), every wave its own pieces) in front of the barrier that
 // opens segment 2i + 3: one tile of flight, as above.  The DMAs are hidden from hipcc (lds_dma16_untracked): it otherwise waits lgkmcnt(0) in front of every consumer of a
 // ds_read while one is in flight, and here the operand reads of P.V and S run beside the flight.
-#define PP_DMA_ROWS(base_, stride_, swz_, kb_, t_, pitch_)                                                          \
-  do {                                                                                                              \
-    int ln_ = lane;                                                                                                 \
-    asm volatile("" : "+v"(ln_));                                                                                   \
-    const int ss_ = ln_ & 15, lr_ = ln_ >> 4;                                                                        \
-    _Pragma("unroll") for (int i_ = 0; i_ < PPT; ++i_) {                                                            \
-      const int row_ = 4 * PPT * wave + 4 * i_ + lr_;                                                               \
-      const uint32_t kr_ = (uint32_t)((kb_) + row_ < len_k ? (kb_) + row_ : (len_k - 1));                           \
-      lds_dma16_untracked((base_) + ((uint64_t)kr_ * (stride_) + (uint32_t)((ss_ ^ (swz_)) << 4)),                  \
-                          (t_) + (4 * PPT * wave + 4 * i_) * (pitch_));                                             \
-    }                                                                                                               \
+#define PP_DMA_ROWS(base_, stride_, swz_, kb_, t_, pitch_)                                                        \
+  do {                                                                                                            \
+    int ln_ = lane;                                                                                               \
+    asm volatile("" : "+v"(ln_));                                                                                 \
+    const int ss_ = ln_ & 15, lr_ = ln_ >> 4;                                                                     \
+    _Pragma("unroll") for (int i_ = 0; i_ < PPT; ++i_) {                                                          \
+      const int row_ = 4 * PPT * wave + 4 * i_ + lr_;                                                             \
+      const uint32_t kr_ = (uint32_t)((kb_) + row_ < len_k ? (kb_) + row_ : (len_k - 1));                         \
+      lds_dma16_untracked((base_) + ((uint64_t)kr_ * (stride_) + (uint32_t)((ss_ ^ (swz_)) << 4)),                \
+                          (t_) + (4 * PPT * wave + 4 * i_) * (pitch_));                                           \
+    }                                                                                                             \
   } while (0)
-#define PP_DMA_K(kb_, kt_) PP_DMA_ROWS(kbase, kstride_b, (row_ & 15), kb_, kt_, PKROW)
-#define PP_DMA_V(kb_, vt_) PP_DMA_ROWS(vbase, vstride_b, (2 * (row_ & 7)), kb_, vt_, PVROW)
+#define PP_DMA_K(kb_, kt_) PP_DMA_ROWS(kbase, kstride_b, (row_ & 15), kb_, kt_, PROW)
+#define PP_DMA_V(kb_, vt_) PP_DMA_ROWS(vbase, vstride_b, (2 * (row_ & 7)), kb_, vt_, PROW)
 
 __global__ __launch_bounds__(512, 2) __attribute__((amdgpu_waves_per_eu(4, 4), amdgpu_num_vgpr(128)))
 void prefill_attn_pp_kernel(PrefillArgs p) {
-  static_assert(PQB == 1 && PWAVES == 8, "the ping-pong form is written for 8 waves x 16 rows");
-  __shared__ __attribute__((aligned(16))) uint8_t ktile0[PKTILE];
-  __shared__ __attribute__((aligned(16))) uint8_t ktile1[PKTILE];
-  __shared__ __attribute__((aligned(16))) uint8_t vtile0[PVTILE];
-  __shared__ __attribute__((aligned(16))) uint8_t vtile1[PVTILE];
+  __shared__ __attribute__((aligned(16))) uint8_t ktile0[PTILE];
+  __shared__ __attribute__((aligned(16))) uint8_t ktile1[PTILE];
+  __shared__ __attribute__((aligned(16))) uint8_t vtile0[PTILE];
+  __shared__ __attribute__((aligned(16))) uint8_t vtile1[PTILE];
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l15 = lane & 15, l4 = lane >> 4;
   int b = blockIdx.z, h = blockIdx.y, qt = gridDim.x - 1 - blockIdx.x;
@@ -424,12 +255,7 @@ void prefill_attn_pp_kernel(PrefillArgs p) {
   const float scale2 = 0.08838834764831845f * 1.4426950408889634f;
   const int qrow = q0 + l15;
   v8h qb[4];
-  {
-    const int qr_c = qrow < len_q ? qrow : (len_q - 1);
-    const half_t* qp = p.q + (size_t)(q_begin + qr_c) * p.q_stride + (size_t)h * PDH + 8 * l4;
-#pragma unroll
-    for (int s = 0; s < 4; ++s) qb[s] = *reinterpret_cast<const v8h*>(qp + 32 * s);
-  }
+  load_q16(p.q, p.q_stride, q_begin, qrow, len_q, h, l4, qb);
   v4f oacc[8];
   float m_run = -1e30f, l_run = 0.0f;
 #pragma unroll
@@ -444,23 +270,10 @@ void prefill_attn_pp_kernel(PrefillArgs p) {
   const uint8_t* kbase = reinterpret_cast<const uint8_t*>(p.k + (size_t)k_begin * p.k_stride + (size_t)hk * PDH);
   const uint8_t* vbase = reinterpret_cast<const uint8_t*>(p.v + (size_t)k_begin * p.v_stride + (size_t)hk * PDH);
   const uint32_t kstride_b = (uint32_t)(p.k_stride * 2), vstride_b = (uint32_t)(p.v_stride * 2);
-  const int trow = 4 * l4 + (l15 >> 2);
-  const int tr_a0 = (trow * PVROW + (l15 & 3) * 8) | ((trow & 7) << 5);
+  const int tr_a0 = pv16_lane_addr(l15, l4);
 
   // ---- the three stages of a tile (the 16-row kernel's own code) ---------------------------------------------------------
-  auto stage_s = [&](const uint8_t* kt, v4f (&st)[4]) {
-#pragma unroll
-    for (int u = 0; u < 4; ++u) st[u] = (v4f){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int key = 16 * u + l15;
-#pragma unroll
-      for (int s = 0; s < 4; ++s) {
-        const v8h a = *reinterpret_cast<const v8h*>(kt + key * PKROW + (((4 * s + l4) ^ l15) << 4));
-        st[u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, qb[s], st[u], 0, 0, 0);
-      }
-    }
-  };
+  auto stage_s = [&](const uint8_t* kt, v4f (&st)[4]) { stage_s16(kt, qb, l15, l4, st); };
   auto stage_softmax = [&](int kb, const v4f (&st)[4], v8h (&pb)[2]) {
     bool full = (kb + PKT <= len_k) && (q_first + PQROWS <= len_q);
     if (p.causal) full = full && (kb + PKT - 1 <= q_first + off);
@@ -511,29 +324,7 @@ void prefill_attn_pp_kernel(PrefillArgs p) {
     }
     m_run = m_new;
   };
-  auto stage_pv = [&](const uint8_t* vt, const v8h (&pb)[2]) {
-    v8h a16[16];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const int kk = i >> 3, c = i & 7;
-      const uint8_t* src = vt + (32 * kk) * PVROW + (tr_a0 ^ (c << 5));
-      const pv4hp lo = __builtin_amdgcn_ds_read_tr16_b64_v4f16(
-          (__attribute__((address_space(3))) pv4hp*)(__attribute__((address_space(3))) void*)(src));
-      const pv4hp hi = __builtin_amdgcn_ds_read_tr16_b64_v4f16(
-          (__attribute__((address_space(3))) pv4hp*)(__attribute__((address_space(3))) void*)(src + 16 * PVROW));
-      a16[i] = (v8h){(half_t)lo[0], (half_t)lo[1], (half_t)lo[2], (half_t)lo[3],
-                     (half_t)hi[0], (half_t)hi[1], (half_t)hi[2], (half_t)hi[3]};
-    }
-#pragma unroll
-    for (int i = 0; i < 16; ++i) oacc[i & 7] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a16[i], pb[i >> 3], oacc[i & 7], 0, 0, 0);
-    __builtin_amdgcn_sched_group_barrier(0x100, 6, 0);
-#pragma unroll
-    for (int i = 0; i < 13; ++i) {
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-      __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-    }
-    __builtin_amdgcn_sched_group_barrier(0x008, 3, 0);
-  };
+  auto stage_pv = [&](const uint8_t* vt, const v8h (&pb)[2]) { stage_pv16(vt, tr_a0, pb, oacc); };
   // barrier that opens a B segment: this wave's DMA pieces have landed, then everybody's
   auto barrier_landed = [&]() {
     lds_dma_wait_all();
@@ -593,21 +384,7 @@ void prefill_attn_pp_kernel(PrefillArgs p) {
     }
     if (first_half) __builtin_amdgcn_s_barrier();
   }
-  // ---- finish ----
-  {
-    const float l = rows4_sum(l_run);
-    if (qrow < len_q) {
-      const float inv = l > 0.0f ? 1.0f / l : 0.0f;
-      half_t* op = p.out + ((size_t)(q_begin + qrow) * p.num_heads + h) * PDH + 4 * l4;
-#pragma unroll
-      for (int c = 0; c < 8; ++c) {
-        typedef _Float16 v4h_t __attribute__((ext_vector_type(4)));
-        const v4h_t o = {(half_t)(oacc[c][0] * inv), (half_t)(oacc[c][1] * inv), (half_t)(oacc[c][2] * inv),
-                         (half_t)(oacc[c][3] * inv)};
-        *reinterpret_cast<v4h_t*>(op + c * 16) = o;
-      }
-    }
-  }
+  store_rows16(p.out, q_begin, qrow, len_q, p.num_heads, h, l4, l_run, oacc);
 }
 #undef PP_DMA_K
 #undef PP_DMA_V
@@ -628,20 +405,17 @@ void prefill_attn_pp_kernel(PrefillArgs p) {
 //     addresses, DMA issue) is amortised over twice the flops.
 // V tile swizzle of this kernel: physical 64-B block = logical block ^ (row & 3) (the four rows a 32-lane half of a
 // transposed read touches sit in four different bank quarters); K tile swizzle as above (slot ^ (row & 15)).
-#ifndef OMNI_PREFILL32_WAVES
-#define OMNI_PREFILL32_WAVES 4
-#endif
-constexpr int P32W = OMNI_PREFILL32_WAVES;
+constexpr int P32W = 4;                                  // waves per workgroup
 constexpr int P32ROWS = 32 * P32W;                       // query rows per workgroup
-constexpr int P32PPT = (PKT * 16) / (64 * P32W);         // 1-KiB DMA pieces of a K (or V) tile per wave
+constexpr int P32PPT = PKT / 4 / P32W;                   // 1-KiB DMA pieces of a K (or V) tile per wave
 typedef float v16f __attribute__((ext_vector_type(16)));
 
 __global__ __launch_bounds__(64 * P32W, 8 / P32W) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void prefill_attn32_kernel(PrefillArgs p) {
-  __shared__ __attribute__((aligned(16))) uint8_t ktile0[PKTILE];
-  __shared__ __attribute__((aligned(16))) uint8_t ktile1[PKTILE];
-  __shared__ __attribute__((aligned(16))) uint8_t vtile0[PVTILE];
-  __shared__ __attribute__((aligned(16))) uint8_t vtile1[PVTILE];
+  __shared__ __attribute__((aligned(16))) uint8_t ktile0[PTILE];
+  __shared__ __attribute__((aligned(16))) uint8_t ktile1[PTILE];
+  __shared__ __attribute__((aligned(16))) uint8_t vtile0[PTILE];
+  __shared__ __attribute__((aligned(16))) uint8_t vtile1[PTILE];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int l32 = lane & 31, hi = lane >> 5, l15 = lane & 15, grp = lane >> 4;
   int b = blockIdx.z, h = blockIdx.y, qt = gridDim.x - 1 - blockIdx.x;
@@ -689,27 +463,27 @@ void prefill_attn32_kernel(PrefillArgs p) {
   do {                                                                                                            \
     int ln_ = lane;                                                                                               \
     asm volatile("" : "+v"(ln_));                                                                                 \
-    const int ss_ = ln_ & 15, lr_ = ln_ >> 4;                                                                      \
+    const int ss_ = ln_ & 15, lr_ = ln_ >> 4;                                                                     \
     _Pragma("unroll") for (int i_ = 0; i_ < P32PPT; ++i_) {                                                       \
       const int row_ = 4 * P32PPT * wave + 4 * i_ + lr_;                                                          \
       const uint32_t kr_ = (uint32_t)((kb_) + row_ < len_k ? (kb_) + row_ : (len_k - 1));                         \
-      lds_dma16_untracked(kbase + ((uint64_t)kr_ * kstride_b + (uint32_t)((ss_ ^ (row_ & 15)) << 4)),                       \
-                (kt_) + (4 * P32PPT * wave + 4 * i_) * PKROW);                                                    \
-      lds_dma16_untracked(vbase + ((uint64_t)kr_ * vstride_b + (uint32_t)((ss_ ^ ((row_ & 3) << 2)) << 4)),                 \
-                (vt_) + (4 * P32PPT * wave + 4 * i_) * PVROW);                                                    \
+      lds_dma16_untracked(kbase + ((uint64_t)kr_ * kstride_b + (uint32_t)((ss_ ^ (row_ & 15)) << 4)),             \
+                (kt_) + (4 * P32PPT * wave + 4 * i_) * PROW);                                                     \
+      lds_dma16_untracked(vbase + ((uint64_t)kr_ * vstride_b + (uint32_t)((ss_ ^ ((row_ & 3) << 2)) << 4)),       \
+                (vt_) + (4 * P32PPT * wave + 4 * i_) * PROW);                                                     \
     }                                                                                                             \
   } while (0)
 
   // LDS addresses.  K operand (key 32u + l32, logical 16-B slot 2s + hi): physical slot (2s + hi) ^ l15.
   int kaddr[8];
 #pragma unroll
-  for (int s = 0; s < 8; ++s) kaddr[s] = l32 * PKROW + (((2 * s + hi) ^ l15) << 4);
+  for (int s = 0; s < 8; ++s) kaddr[s] = l32 * PROW + (((2 * s + hi) ^ l15) << 4);
   // V^T operand: row 4*hi + (l15 >> 2) (+ 16j + 32u, + 8 by immediates), dims 32c + 16*(grp & 1) + 4*(l15 & 3);
   // (row & 3) = l15 >> 2, so the physical 64-B block of logical block c is c ^ (l15 >> 2)
   int vaddr[4];
 #pragma unroll
   for (int c = 0; c < 4; ++c)
-    vaddr[c] = (4 * hi + (l15 >> 2)) * PVROW + ((c ^ (l15 >> 2)) << 6) + 32 * (grp & 1) + 8 * (l15 & 3);
+    vaddr[c] = (4 * hi + (l15 >> 2)) * PROW + ((c ^ (l15 >> 2)) << 6) + 32 * (grp & 1) + 8 * (l15 & 3);
 
   // (the tile DMAs of this kernel are hidden from hipcc -- inline asm -- and waited for by hand: while it knows of a DMA in
   //  flight it puts a full lgkmcnt(0) in front of every consumer of a ds_read, which breaks the read pipelines below)
@@ -732,7 +506,7 @@ void prefill_attn32_kernel(PrefillArgs p) {
       for (int r = 0; r < 16; ++r) st[u][r] = 0.0f;
 #pragma unroll
       for (int s = 0; s < 8; ++s) {
-        const v8h a = *reinterpret_cast<const v8h*>(kt + 32 * u * PKROW + kaddr[s]);
+        const v8h a = *reinterpret_cast<const v8h*>(kt + 32 * u * PROW + kaddr[s]);
         st[u] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, qb[s], st[u], 0, 0, 0);
       }
     }
@@ -801,11 +575,11 @@ void prefill_attn32_kernel(PrefillArgs p) {
       const int u = uj >> 1, j = uj & 1;
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
-        const uint8_t* src = vt + (32 * u + 16 * j) * PVROW + vaddr[c];
+        const uint8_t* src = vt + (32 * u + 16 * j) * PROW + vaddr[c];
         const pv4hp lo = __builtin_amdgcn_ds_read_tr16_b64_v4f16(
             (__attribute__((address_space(3))) pv4hp*)(__attribute__((address_space(3))) void*)(src));
         const pv4hp hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4f16(
-            (__attribute__((address_space(3))) pv4hp*)(__attribute__((address_space(3))) void*)(src + 8 * PVROW));
+            (__attribute__((address_space(3))) pv4hp*)(__attribute__((address_space(3))) void*)(src + 8 * PROW));
         const v8h a = {(half_t)lo[0], (half_t)lo[1], (half_t)lo[2], (half_t)lo[3],
                        (half_t)hi4[0], (half_t)hi4[1], (half_t)hi4[2], (half_t)hi4[3]};
         oacc[c] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, pb[u][j], oacc[c], 0, 0, 0);
@@ -860,8 +634,8 @@ void prefill_attn32_kernel(PrefillArgs p) {
 
 using namespace omni;
 
-static thread_local int g_prefill_variant = OMNI_PREFILL_MFMA32;
-// Tuning / test hook: 0 = the 16-row form (default), 1 = the 32-row form.  Same results within the attention tolerance.
+static thread_local int g_prefill_variant = 0;
+// Tuning / test hook: 0 = the 16-row form (default), 1 = the 32-row form, 2 = the ping-pong form.  Same results within the attention tolerance.
 extern "C" void omni_prefill_set_variant(int variant) { g_prefill_variant = (variant == 1 || variant == 2) ? variant : 0; }
 #ifndef OMNI_PREFILL_XCD_SPLIT_MASKED
 #define OMNI_PREFILL_XCD_SPLIT_MASKED 8
@@ -876,9 +650,7 @@ static int prefill_attention_common(void* out_f16, const void* q_f16, const void
                                     int max_seqlen_q, int num_heads, int num_kv_heads, int head_dim, int causal,
                                     const void* head_mask_type_i32, const void* streaming_info_i32, int gran_log2, void* stream) {
   if (!out_f16 || !q_f16 || !k_f16 || !v_f16 || !cu_seqlens_q_i32 || !cu_seqlens_k_i32) return OMNI_EINVAL;
-  if (head_dim != PDH || batch < 1 || num_heads < 1 || num_kv_heads < 1 || num_heads % num_kv_heads != 0 ||
-      max_seqlen_q < 1 || q_stride % 8 != 0 || k_stride % 8 != 0 || v_stride % 8 != 0 || k_stride < 0 || v_stride < 0 ||
-      k_stride >= (1LL << 31) || v_stride >= (1LL << 31))
+  if (!prefill_layout_ok(head_dim, num_heads, num_kv_heads, q_stride, k_stride, v_stride) || batch < 1 || max_seqlen_q < 1)
     return OMNI_EINVAL;
   if ((head_mask_type_i32 == nullptr) != (streaming_info_i32 == nullptr)) return OMNI_EINVAL;
   PrefillArgs a;

@@ -18,20 +18,12 @@
 // past tile are staged as zeros (scale and offset forced to 0: whatever their bytes decode to, NaN included, never reaches an
 // accumulator) and masked like keys behind the end.  The chunk's own keys then run through the LDS-DMA staging unchanged, with
 // the key index restarting at 0.
-#include "common.h"
+#include "attn_prefill_tile.h"
 #include "kv4_dequant.h"
 
 namespace omni {
 
-constexpr int GDH = 128;
-constexpr int GKT = 64;                // keys per tile
-constexpr int GWAVES = 8;
-constexpr int GPPT = (GKT * 16) / (64 * GWAVES);   // 1-KiB LDS-DMA pieces of a K (or V) tile per wave
-constexpr int GQROWS = 16 * GWAVES;    // 128 query rows per workgroup
-constexpr int GROW = 256;              // bytes per key row of a tile
-constexpr int GTILE = GKT * GROW;
-constexpr int GPACKED_ROW = GDH / 2;   // bytes of one key row of one head in a page
-typedef __fp16 gv4hp __attribute__((__vector_size__(4 * sizeof(__fp16))));
+constexpr int GPACKED_ROW = PDH / 2;   // bytes of one key row of one head in a page
 
 struct PagedPrefillArgs {
   const half_t* q; const half_t* k; const half_t* v; half_t* out;
@@ -43,58 +35,53 @@ struct PagedPrefillArgs {
   int num_heads, num_kv_heads;
 };
 
-__global__ __launch_bounds__(64 * GWAVES, 2) __attribute__((amdgpu_waves_per_eu(4, 4), amdgpu_num_vgpr(128)))
+__global__ __launch_bounds__(64 * PWAVES, 2) __attribute__((amdgpu_waves_per_eu(4, 4), amdgpu_num_vgpr(128)))
 void prefill_attn_paged_kv4_kernel(PagedPrefillArgs p) {
   // (four LDS objects and a loop body per buffer parity, as in attn_prefill.hip: static indices keep the staging of the next
   //  tile apart from the reads of the current one)
-  __shared__ __attribute__((aligned(16))) uint8_t ktile0[GTILE];
-  __shared__ __attribute__((aligned(16))) uint8_t ktile1[GTILE];
-  __shared__ __attribute__((aligned(16))) uint8_t vtile0[GTILE];
-  __shared__ __attribute__((aligned(16))) uint8_t vtile1[GTILE];
+  __shared__ __attribute__((aligned(16))) uint8_t ktile0[PTILE];
+  __shared__ __attribute__((aligned(16))) uint8_t ktile1[PTILE];
+  __shared__ __attribute__((aligned(16))) uint8_t vtile0[PTILE];
+  __shared__ __attribute__((aligned(16))) uint8_t vtile1[PTILE];
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l15 = lane & 15, l4 = lane >> 4;
   const int b = blockIdx.z, h = blockIdx.y, qt = gridDim.x - 1 - blockIdx.x;   // long (late) query tiles first
   const int hk = h / (p.num_heads / p.num_kv_heads);
   const int q_begin = p.cu_q[b], len_q = p.cu_q[b + 1] - q_begin;
-  const int q_first = qt * GQROWS;
+  const int q_first = qt * PQROWS;
   if (q_first >= len_q) return;                                 // (covers len_q = 0)
   const int past = max(p.past[b], 0);
-  const int q_last = min(q_first + GQROWS, len_q) - 1;
+  const int q_last = min(q_first + PQROWS, len_q) - 1;
   const int qrow = q_first + wave * 16 + l15;
   const float scale2 = 0.08838834764831845f * 1.4426950408889634f;   // log2(e)/sqrt(128): scores in the exp2 domain
 
-  v8h qb[4];     // B operand of S^T = K Q^T: Q[row][32s + 8*l4 + (0..7)]
-  {
-    const int qr_c = qrow < len_q ? qrow : (len_q - 1);
-    const half_t* qp = p.q + (size_t)(q_begin + qr_c) * p.q_stride + (size_t)h * GDH + 8 * l4;
-#pragma unroll
-    for (int s = 0; s < 4; ++s) qb[s] = *reinterpret_cast<const v8h*>(qp + 32 * s);
-  }
+  v8h qb[4];
+  load_q16(p.q, p.q_stride, q_begin, qrow, len_q, h, l4, qb);
   v4f oacc[8];
   float m_run = -1e30f, l_run = 0.0f;
 #pragma unroll
   for (int c = 0; c < 8; ++c) oacc[c] = (v4f){0.f, 0.f, 0.f, 0.f};
 
-  const int n_past = (past + GKT - 1) / GKT;          // tiles of the past (the last may be partial)
+  const int n_past = (past + PKT - 1) / PKT;          // tiles of the past (the last may be partial)
   const int f_hi = q_last + 1;                        // fresh keys this workgroup needs (causal): [0, f_hi), f_hi <= len_q
-  const int n_tiles = n_past + (f_hi + GKT - 1) / GKT;
+  const int n_tiles = n_past + (f_hi + PKT - 1) / PKT;
 
   // ---- fresh tiles: LDS-DMA, the swizzles applied on the global side (attn_prefill.hip) ----------------------------------
-  const uint8_t* kbase = reinterpret_cast<const uint8_t*>(p.k + (size_t)q_begin * p.k_stride + (size_t)hk * GDH);
-  const uint8_t* vbase = reinterpret_cast<const uint8_t*>(p.v + (size_t)q_begin * p.v_stride + (size_t)hk * GDH);
+  const uint8_t* kbase = reinterpret_cast<const uint8_t*>(p.k + (size_t)q_begin * p.k_stride + (size_t)hk * PDH);
+  const uint8_t* vbase = reinterpret_cast<const uint8_t*>(p.v + (size_t)q_begin * p.v_stride + (size_t)hk * PDH);
   const uint32_t kstride_b = (uint32_t)(p.k_stride * 2), vstride_b = (uint32_t)(p.v_stride * 2);   // host: < 2^32
 #define PAGED_DMA_TILE(kb_, kt_, vt_)                                                                             \
   do {                                                                                                            \
     int ln_ = lane;                                                                                               \
-    asm volatile("" : "+v"(ln_));   /* opaque per tile: the per-piece lane constants must not be hoisted */         \
-    const int ss_ = ln_ & 15, lr_ = ln_ >> 4;                                                                      \
-    _Pragma("unroll") for (int i_ = 0; i_ < GPPT; ++i_) {                                                         \
-      const int row_ = 4 * GPPT * wave + 4 * i_ + lr_;                                                            \
+    asm volatile("" : "+v"(ln_));   /* opaque per tile: the per-piece lane constants must not be hoisted */       \
+    const int ss_ = ln_ & 15, lr_ = ln_ >> 4;                                                                     \
+    _Pragma("unroll") for (int i_ = 0; i_ < PPT; ++i_) {                                                          \
+      const int row_ = 4 * PPT * wave + 4 * i_ + lr_;                                                             \
       const uint32_t kr_ = (uint32_t)((kb_) + row_ < len_q ? (kb_) + row_ : (len_q - 1));                         \
       lds_dma16(kbase + ((uint64_t)kr_ * kstride_b + (uint32_t)((ss_ ^ (row_ & 15)) << 4)),                       \
-                (kt_) + (4 * GPPT * wave + 4 * i_) * GROW);                                                       \
+                (kt_) + (4 * PPT * wave + 4 * i_) * PROW);                                                        \
       lds_dma16(vbase + ((uint64_t)kr_ * vstride_b + (uint32_t)((ss_ ^ (2 * (row_ & 7))) << 4)),                  \
-                (vt_) + (4 * GPPT * wave + 4 * i_) * GROW);                                                       \
+                (vt_) + (4 * PPT * wave + 4 * i_) * PROW);                                                        \
     }                                                                                                             \
   } while (0)
 
@@ -123,7 +110,7 @@ void prefill_attn_paged_kv4_kernel(PagedPrefillArgs p) {
     v2h d[16];
     kv4_dequant16(praw, (v2h){sc, sc}, (v2h){ch, ch}, d);
     // word i of the 16 bytes = elements 8i .. 8i+7 of the quarter, delivered as the pairs (e_j, e_{j+4}): back to natural order
-    uint8_t* rowp = (is_v ? vt : kt) + pkey * GROW;
+    uint8_t* rowp = (is_v ? vt : kt) + pkey * PROW;
     const int swz = is_v ? 2 * (pkey & 7) : (pkey & 15);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -133,10 +120,7 @@ void prefill_attn_paged_kv4_kernel(PagedPrefillArgs p) {
     }
   };
 
-  // V^T operand: row 4*l4 + l15/4 (+16, +32, +48 by immediates), 8 B at logical offset 32c + 8*(l15&3); the physical
-  // 32-B block of logical block c is c ^ (row & 7)
-  const int trow = 4 * l4 + (l15 >> 2);
-  const int tr_a0 = (trow * GROW + (l15 & 3) * 8) | ((trow & 7) << 5);   // address of logical block c: tr_a0 ^ (c << 5)
+  const int tr_a0 = pv16_lane_addr(l15, l4);
 
   if (n_past > 0) {
     past_request(0);
@@ -154,9 +138,9 @@ void prefill_attn_paged_kv4_kernel(PagedPrefillArgs p) {
     uint8_t* kt_next = B ? ktile0 : ktile1;
     uint8_t* vt_next = B ? vtile0 : vtile1;
     const bool cur_past = t < n_past;
-    const int kb = GKT * (cur_past ? t : t - n_past);          // first key of the tile, counted inside its own phase
+    const int kb = PKT * (cur_past ? t : t - n_past);          // first key of the tile, counted inside its own phase
     const bool next_any = t + 1 < n_tiles, next_past = t + 1 < n_past;
-    const int kb_next = GKT * (next_past ? t + 1 : t + 1 - n_past);
+    const int kb_next = PKT * (next_past ? t + 1 : t + 1 - n_past);
     // the keys of this phase end at klim; the causal diagonal only exists in the fresh phase (coff: key <= qrow + coff)
     const int klim = cur_past ? past : len_q;
     const int coff = cur_past ? (1 << 30) : 0;
@@ -165,18 +149,7 @@ void prefill_attn_paged_kv4_kernel(PagedPrefillArgs p) {
     // ---- S^T tile: 4 blocks of 16 keys ------------------------------------------------------------------------------
     __builtin_amdgcn_s_setprio(1);
     v4f st[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) st[u] = (v4f){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int key = 16 * u + l15;
-#pragma unroll
-      for (int s = 0; s < 4; ++s) {
-        const v8h a = *reinterpret_cast<const v8h*>(kt + key * GROW + (((4 * s + l4) ^ l15) << 4));
-        st[u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, qb[s], st[u], 0, 0, 0);
-      }
-    }
-    // st[u][r] = K[kb + 16u + 4*l4 + r] . Q[qrow]
+    stage_s16(kt, qb, l15, l4, st);
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_setprio(0);
     // ... and go to the other buffer (every wave left it at the previous barrier) behind them: dequant + tile writes of a
@@ -185,7 +158,7 @@ void prefill_attn_paged_kv4_kernel(PagedPrefillArgs p) {
     else if (next_any) PAGED_DMA_TILE(kb_next, kt_next, vt_next);
     __builtin_amdgcn_sched_barrier(0);
     // does any (row, key) pair of this workgroup's tile need the mask?  (workgroup-uniform)
-    const bool full = (kb + GKT <= klim) && (q_first + GQROWS <= len_q) && (kb + GKT - 1 <= q_first + coff);
+    const bool full = (kb + PKT <= klim) && (q_first + PQROWS <= len_q) && (kb + PKT - 1 <= q_first + coff);
     // ---- online softmax (per query row = per lane column), probabilities straight into the B operand ------------------
     v8h pb[2];
     {
@@ -232,32 +205,8 @@ void prefill_attn_paged_kv4_kernel(PagedPrefillArgs p) {
       }
       m_run = m_new;
     }
-    // ---- O^T += V^T P^T: transposed reads three steps ahead of the MFMAs (attn_prefill.hip) -----------------------------
     __builtin_amdgcn_s_setprio(1);
-    {
-      v8h a16[16];
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        const int kk = i >> 3, c = i & 7;
-        const uint8_t* src = vt + (32 * kk) * GROW + (tr_a0 ^ (c << 5));
-        const gv4hp lo = __builtin_amdgcn_ds_read_tr16_b64_v4f16(
-            (__attribute__((address_space(3))) gv4hp*)(__attribute__((address_space(3))) void*)(src));
-        const gv4hp hi = __builtin_amdgcn_ds_read_tr16_b64_v4f16(
-            (__attribute__((address_space(3))) gv4hp*)(__attribute__((address_space(3))) void*)(src + 16 * GROW));
-        a16[i] = (v8h){(half_t)lo[0], (half_t)lo[1], (half_t)lo[2], (half_t)lo[3],
-                       (half_t)hi[0], (half_t)hi[1], (half_t)hi[2], (half_t)hi[3]};
-      }
-#pragma unroll
-      for (int i = 0; i < 16; ++i)
-        oacc[i & 7] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a16[i], pb[i >> 3], oacc[i & 7], 0, 0, 0);
-      __builtin_amdgcn_sched_group_barrier(0x100, 6, 0);          // DS reads of steps 0..2
-#pragma unroll
-      for (int i = 0; i < 13; ++i) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);        // MFMA of step i
-        __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);        // DS reads of step i + 3
-      }
-      __builtin_amdgcn_sched_group_barrier(0x008, 3, 0);
-    }
+    stage_pv16(vt, tr_a0, pb, oacc);
     __builtin_amdgcn_s_setprio(0);
     __syncthreads();     // the next tile has landed
     ++t;
@@ -267,18 +216,7 @@ void prefill_attn_paged_kv4_kernel(PagedPrefillArgs p) {
     if (t >= n_tiles) break;
     tile_step(IntTag<1>{});
   }
-  // ---- finish: row sum over the 4 lanes of a query row, normalise, store ------------------------------------------------
-  const float l = rows4_sum(l_run);
-  if (qrow >= len_q) return;
-  const float inv = l > 0.0f ? 1.0f / l : 0.0f;
-  half_t* op = p.out + ((size_t)(q_begin + qrow) * p.num_heads + h) * GDH + 4 * l4;
-#pragma unroll
-  for (int c = 0; c < 8; ++c) {
-    typedef _Float16 v4h_t __attribute__((ext_vector_type(4)));
-    const v4h_t o = {(half_t)(oacc[c][0] * inv), (half_t)(oacc[c][1] * inv), (half_t)(oacc[c][2] * inv),
-                     (half_t)(oacc[c][3] * inv)};
-    *reinterpret_cast<v4h_t*>(op + c * 16) = o;
-  }
+  store_rows16(p.out, q_begin, qrow, len_q, p.num_heads, h, l4, l_run, oacc);
 }
 #undef PAGED_DMA_TILE
 
@@ -292,11 +230,8 @@ extern "C" int omni_prefill_attention_paged_kv4(void* out_f16, const void* q_f16
                                                 const void* kv_pointers_i64, int batch, int max_blocks, int tokens_per_block,
                                                 int max_seqlen_q, int num_heads, int num_kv_heads, int head_dim, void* stream) {
   if (batch < 0 || max_seqlen_q < 0) return OMNI_EINVAL;
-  if (head_dim != GDH || num_heads < 1 || num_kv_heads < 1 || num_heads % num_kv_heads != 0 || tokens_per_block < 16 ||
-      (tokens_per_block & (tokens_per_block - 1)) != 0 || max_blocks < 0)
-    return OMNI_EINVAL;
-  if (q_stride % 8 != 0 || k_stride % 8 != 0 || v_stride % 8 != 0 || q_stride < 0 || k_stride < 0 || v_stride < 0 ||
-      k_stride >= (1LL << 31) || v_stride >= (1LL << 31))      // 32-bit byte strides in the tile addressing
+  if (!prefill_layout_ok(head_dim, num_heads, num_kv_heads, q_stride, k_stride, v_stride) || q_stride < 0 ||
+      tokens_per_block < 16 || (tokens_per_block & (tokens_per_block - 1)) != 0 || max_blocks < 0)
     return OMNI_EINVAL;
   if (batch == 0 || max_seqlen_q == 0) return OMNI_OK;        // no query token: nothing to do
   if (!out_f16 || !q_f16 || !k_new_f16 || !v_new_f16 || !cu_seqlens_q_i32 || !past_lens_i32 || !kv_pointers_i64)
@@ -312,7 +247,7 @@ extern "C" int omni_prefill_attention_paged_kv4(void* out_f16, const void* q_f16
   while ((1 << a.tpb_log2) < tokens_per_block) ++a.tpb_log2;
   a.num_heads = num_heads; a.num_kv_heads = num_kv_heads;
   // one workgroup per (128 query rows, q head, sequence); the kernel takes blockIdx.x in reverse: long tiles first
-  const dim3 grid((max_seqlen_q + GQROWS - 1) / GQROWS, num_heads, batch);
-  hipLaunchKernelGGL(prefill_attn_paged_kv4_kernel, grid, dim3(64 * GWAVES), 0, (hipStream_t)stream, a);
+  const dim3 grid((max_seqlen_q + PQROWS - 1) / PQROWS, num_heads, batch);
+  hipLaunchKernelGGL(prefill_attn_paged_kv4_kernel, grid, dim3(64 * PWAVES), 0, (hipStream_t)stream, a);
   return omni_launch_status();
 }
