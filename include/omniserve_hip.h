@@ -445,6 +445,28 @@ int omni_prefill_attention_paged_kv4(void* out_f16, const void* q_f16, const voi
                                      const void* cu_seqlens_q_i32, const void* past_lens_i32,
                                      const void* kv_pointers_i64, int batch, int max_blocks, int tokens_per_block,
                                      int max_seqlen_q, int num_heads, int num_kv_heads, int head_dim, void* stream);
+/* Project extension (no reference counterpart): multi-token decode attention -- omni_prefill_attention_paged_kv4's semantics
+ * for 0 <= len_q <= 8 new tokens per sequence (speculative decoding's verify step, multi-token heads), built for a long past:
+ * one workgroup serves all (num_heads / num_kv_heads) x len_q query rows of a (sequence, kv head), so a page is dequantised once
+ * per kv head, and the past is split over workgroups whose f32 partials (unnormalised accumulator, running max, sum) go
+ * through `workspace` and are merged in split order (same inputs -> same bits).  The arguments up to head_dim are
+ * omni_prefill_attention_paged_kv4's; max_past is the host's bound on past_lens[] (it sizes the split; the lengths stay on
+ * the device); workspace: omni_decode_attention_multi_kv4_workspace_bytes() bytes, 16-byte aligned.  A sequence longer than
+ * max_seqlen_q is cut to its first max_seqlen_q tokens.  -EINVAL: max_seqlen_q > 8, head_dim != 128, tokens_per_block not a
+ * power of two >= 16, num_heads % num_kv_heads != 0, k / v byte strides >= 2^32; -ENOMEM: workspace NULL or too small.
+ * batch = 0 or max_seqlen_q = 0 returns 0 and launches nothing. */
+int omni_decode_attention_multi_kv4(void* out_f16, const void* q_f16, const void* k_new_f16, const void* v_new_f16,
+                                    int64_t q_stride, int64_t k_stride, int64_t v_stride,
+                                    const void* cu_seqlens_q_i32, const void* past_lens_i32,
+                                    const void* kv_pointers_i64, int batch, int max_blocks, int tokens_per_block,
+                                    int max_seqlen_q, int num_heads, int num_kv_heads, int head_dim, int max_past,
+                                    void* workspace, size_t workspace_bytes, void* stream);
+/* Project extension (no reference counterpart): scratch bytes for omni_decode_attention_multi_kv4 -- enough for the planner's
+ * split count and for every setting of the override below. */
+size_t omni_decode_attention_multi_kv4_workspace_bytes(int batch, int num_heads, int max_seqlen_q, int max_past);
+/* Project extension (no reference counterpart): tuning / test hook -- force the number of KV splits of
+ * omni_decode_attention_multi_kv4 (at most 16; 0 = the planner decides).  Splits that hold no past token contribute nothing. */
+void omni_decode_attention_multi_kv4_set_split_override(int nsplit);
 /* Tuning / test hook: 0 = 16 query rows per wave (16x16x32 MFMA, default), 1 = 32 rows per wave (32x32x16 MFMA), 2 = the 16-row
  * form on the 8-wave ping-pong schedule (waves 4-7 one segment behind waves 0-3; same results within the attention tolerance). */
 void omni_prefill_set_variant(int variant);

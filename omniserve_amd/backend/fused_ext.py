@@ -535,18 +535,9 @@ def kv4_prefill_write_at(qkv, seq_lens, past_lens, padding_offset, kv_pointers, 
     _lib.check(rc, what)
 
 
-def prefill_attention_paged_kv4(q, k_new, v_new, cu_seqlens_q, past_lens, kv_pointers, tokens_per_block, max_seqlen_q,
-                                causal=True, head_mask_type=None, streaming_info=None):
-    """Causal prefill attention whose first past_lens[b] keys / values of sequence b come from the KV4 pages (fp16 dequant, as the
-    decode attention reads them) and whose last len_q keys / values are the call's own fp16 k_new / v_new -- the page slots of
-    those tokens are not read.  q [Lq, Hq, 128], k_new / v_new [Lq, Hkv, 128] fp16 with contiguous heads (token-strided views of
-    the qkv buffer, already rotated by kv4_prefill_write_at); cu_seqlens_q int32 [B+1], past_lens int32 [B], kv_pointers int64
-    [B, 2, blocks].  -> out fp16 [Lq, Hq, 128].  Dense heads and the causal mask only."""
-    what = "fused_ext.prefill_attention_paged_kv4"
-    if not causal:
-        raise NotImplementedError("%s: only the causal mask is implemented" % what)
-    if head_mask_type is not None or streaming_info is not None:
-        raise NotImplementedError("%s: streaming heads are not implemented (all heads are dense)" % what)
+def _check_paged_attention_args(what, q, k_new, v_new, cu_seqlens_q, past_lens, kv_pointers, tokens_per_block):
+    """The tensor checks that the attentions over quantised past + fresh tokens share (prefill_attention_paged_kv4,
+    decode_attention_multi_kv4): one copy, so that the two raise the same errors.  -> (B, tokens_per_block)."""
     _lib.require_cuda(q, k_new, v_new, cu_seqlens_q, past_lens, kv_pointers)
     if q.dtype != torch.float16 or q.dim() != 3 or q.shape[-1] != 128:
         raise RuntimeError("%s: q must be fp16 [tokens, heads, 128]" % what)
@@ -569,6 +560,22 @@ def prefill_attention_paged_kv4(q, k_new, v_new, cu_seqlens_q, past_lens, kv_poi
     tpb = int(tokens_per_block)
     if tpb < 16 or tpb & (tpb - 1):
         raise RuntimeError("%s: tokens_per_block must be a power of two >= 16" % what)
+    return B, tpb
+
+
+def prefill_attention_paged_kv4(q, k_new, v_new, cu_seqlens_q, past_lens, kv_pointers, tokens_per_block, max_seqlen_q,
+                                causal=True, head_mask_type=None, streaming_info=None):
+    """Causal prefill attention whose first past_lens[b] keys / values of sequence b come from the KV4 pages (fp16 dequant, as the
+    decode attention reads them) and whose last len_q keys / values are the call's own fp16 k_new / v_new -- the page slots of
+    those tokens are not read.  q [Lq, Hq, 128], k_new / v_new [Lq, Hkv, 128] fp16 with contiguous heads (token-strided views of
+    the qkv buffer, already rotated by kv4_prefill_write_at); cu_seqlens_q int32 [B+1], past_lens int32 [B], kv_pointers int64
+    [B, 2, blocks].  -> out fp16 [Lq, Hq, 128].  Dense heads and the causal mask only."""
+    what = "fused_ext.prefill_attention_paged_kv4"
+    if not causal:
+        raise NotImplementedError("%s: only the causal mask is implemented" % what)
+    if head_mask_type is not None or streaming_info is not None:
+        raise NotImplementedError("%s: streaming heads are not implemented (all heads are dense)" % what)
+    B, tpb = _check_paged_attention_args(what, q, k_new, v_new, cu_seqlens_q, past_lens, kv_pointers, tokens_per_block)
     out = torch.empty((q.shape[0], q.shape[1], 128), dtype=torch.float16, device=q.device)
     if q.shape[0] == 0 or B == 0:
         return out
@@ -576,5 +583,56 @@ def prefill_attention_paged_kv4(q, k_new, v_new, cu_seqlens_q, past_lens, kv_poi
         out.data_ptr(), q.data_ptr(), k_new.data_ptr(), v_new.data_ptr(), q.stride(0), k_new.stride(0), v_new.stride(0),
         cu_seqlens_q.data_ptr(), past_lens.data_ptr(), kv_pointers.data_ptr(), B, kv_pointers.shape[2], tpb,
         int(max_seqlen_q), q.shape[1], k_new.shape[1], 128, _lib.current_stream())
+    _lib.check(rc, what)
+    return out
+
+
+# ---- multi-token decode step: split-KV attention for 1 - 8 new tokens over the KV4 pages -------------
+DECODE_MULTI_MAX_Q = 8
+
+
+class DecodeMultiTooManyTokens(ValueError):
+    """decode_attention_multi_kv4 serves at most DECODE_MULTI_MAX_Q new tokens per sequence (longer chunks: the paged prefill)."""
+
+
+def decode_attention_multi_kv4_set_split_override(nsplit):
+    """Tuning / test hook: force the KV split count of decode_attention_multi_kv4 (at most 16); 0: the planner decides."""
+    _lib.lib().omni_decode_attention_multi_kv4_set_split_override(int(nsplit))
+
+
+def decode_attention_multi_kv4_workspace_bytes(batch, num_heads, max_seqlen_q, max_past):
+    return int(_lib.lib().omni_decode_attention_multi_kv4_workspace_bytes(int(batch), int(num_heads), int(max_seqlen_q),
+                                                                          int(max_past)))
+
+
+def decode_attention_multi_kv4(q, k_new, v_new, cu_seqlens_q, past_lens, kv_pointers, tokens_per_block, max_seqlen_q, max_past,
+                               workspace=None):
+    """prefill_attention_paged_kv4 for 0 - 8 new tokens per sequence against a long past: one sweep of a kv head's pages serves
+    all of its q heads and all new tokens, and the past is split over workgroups (merged in a fixed order: same inputs, same
+    bits).  Same tensors and checks as prefill_attention_paged_kv4; max_seqlen_q <= 8 bounds the new tokens per sequence and
+    max_past bounds past_lens (the host's numbers: the lengths stay on the device).  workspace: uint8 device tensor of at
+    least decode_attention_multi_kv4_workspace_bytes(...) bytes, allocated (and kept) here when None.
+    -> out fp16 [Lq, Hq, 128]."""
+    what = "fused_ext.decode_attention_multi_kv4"
+    if int(max_seqlen_q) > DECODE_MULTI_MAX_Q:
+        raise DecodeMultiTooManyTokens("%s: max_seqlen_q = %d, at most %d new tokens per sequence"
+                                       % (what, int(max_seqlen_q), DECODE_MULTI_MAX_Q))
+    _lib.require_cuda(workspace)
+    B, tpb = _check_paged_attention_args(what, q, k_new, v_new, cu_seqlens_q, past_lens, kv_pointers, tokens_per_block)
+    if int(max_past) < 0 or int(max_past) > kv_pointers.shape[2] * tpb:
+        raise RuntimeError("%s: max_past must be non-negative and fit the block table" % what)
+    out = torch.empty((q.shape[0], q.shape[1], 128), dtype=torch.float16, device=q.device)
+    if q.shape[0] == 0 or B == 0 or int(max_seqlen_q) < 1:
+        return out
+    if workspace is None:
+        workspace = _lib.workspace(decode_attention_multi_kv4_workspace_bytes(B, q.shape[1], max_seqlen_q, max_past), q.device,
+                                   "decode_multi")
+    elif workspace.dtype != torch.uint8 or not workspace.is_contiguous():
+        raise RuntimeError("%s: workspace must be a contiguous uint8 tensor" % what)
+    rc = _lib.lib().omni_decode_attention_multi_kv4(
+        out.data_ptr(), q.data_ptr(), k_new.data_ptr(), v_new.data_ptr(), q.stride(0), k_new.stride(0), v_new.stride(0),
+        cu_seqlens_q.data_ptr(), past_lens.data_ptr(), kv_pointers.data_ptr(), B, kv_pointers.shape[2], tpb,
+        int(max_seqlen_q), q.shape[1], k_new.shape[1], 128, int(max_past), workspace.data_ptr(), workspace.numel(),
+        _lib.current_stream())
     _lib.check(rc, what)
     return out

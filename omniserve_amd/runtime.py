@@ -122,6 +122,15 @@ class W4A8Linear:
         return sh
 
 
+def accept_lengths(draft, pred):
+    """Tokens per sequence that a multi-token step keeps.  draft int64 [B, n]: column 0 the pending token, columns 1 .. the
+    drafted continuation; pred int64 [B, n]: the model's token behind draft[b, :j + 1].  m[b] = 1 + the number of LEADING j
+    with draft[b, j + 1] == pred[b, j] (a match behind a mismatch does not count): the pending token is always kept, and each
+    drafted token as long as it is what the model would have produced.  Pure tensor arithmetic (CPU or device).  -> int64 [B]."""
+    match = (draft[:, 1:] == pred[:, :-1]).to(torch.int64)
+    return 1 + torch.cumprod(match, dim=1).sum(dim=1)
+
+
 class DecodeRunner:
     """bs sequences with `context` cached tokens each; step() decodes one token per sequence."""
 
@@ -702,8 +711,7 @@ class DecodeRunner:
         (fused_ext.prefill_attention_paged_kv4: quantised past, fresh chunk) in place of its writer / attention pair.  Updates
         self.lengths and leaves the next token in self.tokens.  `tokens`: B * new_len ids, sequence after sequence (default:
         random ids).  With nothing in the pools yet (every length 0) this is prefill(new_len, tokens) itself."""
-        from .backend.fused_attention_fine_grained_dense import compute_padding_offsets
-        c, B, dev = self.cfg, self.B, self.device
+        c, B = self.cfg, self.B
         n = int(new_len)
         past_max = int(self.lengths.max().item())
         if n < 1:
@@ -712,6 +720,24 @@ class DecodeRunner:
             raise ValueError("lengths + new_len does not fit the runner's KV pools")
         if past_max == 0:
             return self.prefill(n, tokens)
+        if tokens is None:
+            tokens = torch.randint(0, c.vocab, (B * n,), device=self.device, generator=self.gen)
+        elif tokens.numel() != B * n:
+            raise ValueError("extend expects %d tokens, got %d" % (B * n, tokens.numel()))
+        x = self._extend_rows(n, tokens, past_max, fused_ext.prefill_attention_paged_kv4)
+        self.x.copy_(x.view(B, n, c.hidden)[:, n - 1])
+        layernorm_ops.rms_norm(self.normed, self.x, self.final_norm, c.eps, False)
+        logits = torch.matmul(self.normed, self.lm_head.t())
+        self.tokens.copy_(torch.argmax(logits, dim=-1))
+        self.lengths.add_(n)
+
+    def _extend_rows(self, n, tokens, past_max, attention):
+        """The decoder layers on B * n rows that continue the sequences in the KV pools (extend(), verify()): writes the rows'
+        keys / values at positions lengths + i and returns the rows' final hidden states [B * n, hidden] (a view of a buffer
+        the next call reuses).  `attention(q, k, v, cu, past, table, tpb, n)`: the attention over quantised past + fresh rows.
+        self.lengths is left alone."""
+        from .backend.fused_attention_fine_grained_dense import compute_padding_offsets
+        c, B, dev = self.cfg, self.B, self.device
         T = B * n
         hq, hk, d = self.hl, self.kl, c.head_dim
         f16, i8 = torch.float16, torch.int8
@@ -729,10 +755,6 @@ class DecodeRunner:
             self._prefill_bufs = buf
         x, qh, qi, qa, qkv, proj, gu = (buf[name][:T] for name in ("x", "qh", "qi", "qa", "qkv", "proj", "gu"))
         sB, mB, sA, mA = (buf[name][:T] for name in ("s1", "m1", "s2", "m2"))
-        if tokens is None:
-            tokens = torch.randint(0, c.vocab, (T,), device=dev, generator=self.gen)
-        elif tokens.numel() != T:
-            raise ValueError("extend expects %d tokens, got %d" % (T, tokens.numel()))
         torch.index_select(self.embed, 0, tokens.reshape(-1), out=x)
         lens = torch.full((B,), n, dtype=torch.int32, device=dev)
         past = self.lengths.clone()
@@ -754,7 +776,7 @@ class DecodeRunner:
             Ly["qkv"].forward(qh, sB, mB, qkv)
             fused_ext.kv4_prefill_write_at(qkv, lens, past, pad, self.block_tables[li], hq, hk, n, self.tpb, past_max + n,
                                            c.rope_theta, 1.0, 1 << 20)
-            attn = fused_ext.prefill_attention_paged_kv4(q, k, v, cu, past, self.block_tables[li], self.tpb, n)
+            attn = attention(q, k, v, cu, past, self.block_tables[li], self.tpb, n)
             if per_chn:
                 fused_kernels.invoke_quant_fuse_sum(qa, attn.view(T, hq * d), mA, sA)
             else:
@@ -767,11 +789,46 @@ class DecodeRunner:
             Ly["down"].forward(qi, sA, mA, proj)
             self._all_reduce(proj)
         x.add_(proj)
-        self.x.copy_(x.view(B, n, c.hidden)[:, n - 1])
-        layernorm_ops.rms_norm(self.normed, self.x, self.final_norm, c.eps, False)
-        logits = torch.matmul(self.normed, self.lm_head.t())
-        self.tokens.copy_(torch.argmax(logits, dim=-1))
-        self.lengths.add_(n)
+        return x
+
+    def verify(self, draft):
+        """One multi-token decode step (the verify step of speculative decoding): score n = draft.shape[1] <= 8 positions per
+        sequence in one pass over the weights.  draft int64 [B, n]: column 0 is self.tokens (the pending token, not yet in the
+        pools), columns 1 .. the drafted continuation.  extend()'s layer sequence on B * n rows with the split-KV multi-token
+        attention (fused_ext.decode_attention_multi_kv4) in place of the paged prefill attention, then final norm, lm_head and
+        arg-max at ALL n positions: pred int64 [B, n], pred[b, j] = the model's token behind draft[b, :j + 1].  m =
+        accept_lengths(draft, pred) tokens per sequence are kept: lengths += m, tokens = pred[b, m - 1], self.x / self.normed =
+        the hidden state of the last accepted position (as extend() leaves them).  Rollback: the rejected tokens' page slots
+        keep their bytes; they lie at positions >= lengths, which no kernel reads and later appends overwrite.  Eager launches
+        (capturing the step in a HIP graph is the follow-up).  -> (pred, m)."""
+        c, B = self.cfg, self.B
+        if draft.dim() != 2 or draft.shape[0] != B or draft.dtype != torch.int64:
+            raise ValueError("verify expects an int64 [B, n] draft")
+        n = int(draft.shape[1])
+        if n < 1 or n > fused_ext.DECODE_MULTI_MAX_Q:
+            raise ValueError("verify takes 1 to %d positions per sequence, got %d" % (fused_ext.DECODE_MULTI_MAX_Q, n))
+        draft = draft.to(self.device)
+        if not bool((draft[:, 0] == self.tokens).all().item()):
+            raise ValueError("verify: column 0 of the draft must be the runner's pending tokens")
+        past_max = int(self.lengths.max().item())
+        if past_max + n + 1 > self.max_context:
+            raise ValueError("lengths + draft length does not fit the runner's KV pools")
+
+        def attention(q, k, v, cu, past, table, tpb, n_):
+            return fused_ext.decode_attention_multi_kv4(q, k, v, cu, past, table, tpb, n_, past_max)
+
+        x = self._extend_rows(n, draft.reshape(-1), past_max, attention)
+        normed = torch.empty_like(x)
+        layernorm_ops.rms_norm(normed, x, self.final_norm, c.eps, False)
+        pred = torch.argmax(torch.matmul(normed, self.lm_head.t()), dim=-1).view(B, n)
+        m = accept_lengths(draft, pred)
+        last = (m - 1).view(B, 1)
+        pick = last.view(B, 1, 1).expand(B, 1, c.hidden)
+        self.x.copy_(x.view(B, n, c.hidden).gather(1, pick).squeeze(1))
+        self.normed.copy_(normed.view(B, n, c.hidden).gather(1, pick).squeeze(1))
+        self.tokens.copy_(pred.gather(1, last).squeeze(1))
+        self.lengths.add_(m.to(torch.int32))
+        return pred, m
 
     def _all_reduce(self, buf):
         if self.tp_size > 1:
