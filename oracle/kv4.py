@@ -445,6 +445,19 @@ def decode_attention_fine_grained(q_h, k_h, v_h, lengths, fg: FineGrainedKV, rop
 
 
 # ---- host-side logic of the LServe path (pure Python / torch upstream), pinned by tests/golden/host_logic.json -------
+def topk_pages(stats, subs, total_pages, k):
+    """The page choice itself, stated once: stats [B, Hq, >= (total_pages - 1) * subs] selector scores -> int32 [B, Hq, k + 1].
+    Page score = maximum over the page's `subs` sub-chunks; the k best pages of [0, total_pages - 1) in descending score order
+    (compared in float32: -0 == +0; stable, so ties go to the lower page), then the newest page total_pages - 1."""
+    stats = np.asarray(stats)
+    B, Hq = stats.shape[:2]
+    n = total_pages - 1
+    page_scores = stats[:, :, : n * subs].reshape(B, Hq, n, subs).max(axis=-1)
+    order = np.argsort(-page_scores.astype(np.float32), axis=-1, kind="stable")[:, :, :k]
+    newest = np.full((B, Hq, 1), n, np.int64)
+    return np.concatenate([order, newest], axis=-1).astype(np.int32)
+
+
 def select_topk_pages(stats, tokens_per_block, sub_chunk, budget_tokens, timestep):
     """decoding_attention.py:88-142 (DecodingAttentionWrapper.dynamic_select_topk_pages) after the selector kernel:
     stats [B, Hq, padded_sub_chunks] -> int32 [B, Hq, P].  timestep = history length (current token excluded).
@@ -458,12 +471,9 @@ def select_topk_pages(stats, tokens_per_block, sub_chunk, budget_tokens, timeste
         pages = np.arange(0, timestep // tokens_per_block + 1, dtype=np.int32)
         return np.broadcast_to(pages, (B, Hq, pages.size)).copy()
     subs = tokens_per_block // sub_chunk
-    page_scores = stats.reshape(B, Hq, -1, subs).max(axis=-1)
-    total = page_scores.shape[-1]
+    total = stats.shape[-1] // subs
     k = min(max(3, min(budget_tokens, timestep) // tokens_per_block), total) - 1
-    order = np.argsort(-page_scores[:, :, : total - 1].astype(np.float32), axis=-1, kind="stable")[:, :, :k]
-    newest = np.full((B, Hq, 1), total - 1, np.int64)
-    return np.concatenate([order, newest], axis=-1).astype(np.int32)
+    return topk_pages(stats, subs, total, k)
 
 
 def head_classes(full_attention_heads, num_heads):

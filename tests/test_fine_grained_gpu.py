@@ -70,12 +70,15 @@ class Case:
         assert np.array_equal(sk, self.sk.pool), "streaming K pages differ (%s)" % what
         assert np.array_equal(sv, self.sv.pool), "streaming V pages differ (%s)" % what
 
-    def prefill(self):
+    def prefill(self, qkv=None):
+        """qkv: the prompt's fp16 [tokens, (Hq + 2 Hk) * D] rows (N(0, 1) by default)."""
         import omniserve_backend.fused_attention_fine_grained_dense as fa
         Hq, Hk = self.Hq, self.Hk
         T = sum(self.seq_lens)
         max_len = max(self.seq_lens)
-        qkv = self.rng.standard_normal((T, (Hq + 2 * Hk) * D)).astype(np.float16)
+        if qkv is None:
+            qkv = self.rng.standard_normal((T, (Hq + 2 * Hk) * D)).astype(np.float16)
+        assert qkv.shape == (T, (Hq + 2 * Hk) * D) and qkv.dtype == np.float16
         want = kv4.prefill_write_fine_grained(qkv, self.seq_lens, self.fg, Hq, Hk, D, ROPE_BASE, self.scale)
         cu = np.concatenate([[0], np.cumsum(self.seq_lens)]).astype(np.int32)
         pad = fa.compute_padding_offsets(to_dev(cu), max_len, T)
@@ -98,14 +101,15 @@ class Case:
         self.check_pools("prefill")
         self.qkv_post = want
 
-    def decode(self, steps, dyn_fn=None):
+    def decode(self, steps, dyn_fn=None, qkv_fn=None):
+        """qkv_fn(step) -> the step's fp16 [B, (Hq + 2 Hk) * D] rows (N(0, 1) by default)."""
         import omniserve_backend.fused_attention_fine_grained_dense as fad
         import omniserve_backend.fused_attention_fine_grained_sparse as fas
         Hq, Hk, B = self.Hq, self.Hk, self.B
         lens = np.asarray(self.seq_lens, np.int32)
         for step in range(steps):
             lens = lens + 1
-            qkv = self.rng.standard_normal((B, (Hq + 2 * Hk) * D)).astype(np.float16)
+            qkv = qkv_fn(step) if qkv_fn else self.rng.standard_normal((B, (Hq + 2 * Hk) * D)).astype(np.float16)
             q = qkv[:, : Hq * D].reshape(B, Hq, D)
             k = qkv[:, Hq * D:(Hq + Hk) * D].reshape(B, Hk, D)
             v = qkv[:, (Hq + Hk) * D:].reshape(B, Hk, D)

@@ -290,6 +290,7 @@ def test_page_selector_ragged_ratio(g):
     idx = out.cpu().long()
     assert (idx[:, :, kk] == pages - 1).all()
     assert torch.equal(torch.gather(page_scores, 2, idx[:, :, :kk]), want_vals)
+    assert np.array_equal(out.cpu().numpy(), kv4.topk_pages(sc.cpu().numpy(), subs, pages, kk))      # the same pages, in order
 
 
 # ---------------------------------------------------------------------------------------------------------------

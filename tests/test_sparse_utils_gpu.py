@@ -65,7 +65,8 @@ def test_paged_min_max_pool_and_selector(seq_lens, Hin, pooled):
 @pytest.mark.parametrize("B,H,pages,subs,k", [(1, 32, 4001, 4, 63), (2, 8, 12, 4, 2), (1, 4, 300, 2, 299), (3, 2, 5000, 1, 1024)])
 def test_select_topk_pages_matches_torch(B, H, pages, subs, k):
     """fused_ext.select_topk_pages == the torch sequence of decoding_attention.py:132-142 (max over sub-chunks, topk of
-    all pages but the newest, newest page appended); ties may be broken differently, so the chosen SCORES are compared."""
+    all pages but the newest, newest page appended); torch may break ties differently, so against torch the chosen SCORES are
+    compared; the pages themselves are compared with oracle.kv4.topk_pages, which states the kernel's tie rule."""
     from omniserve_amd.backend import fused_ext
     g = torch.Generator(device="cpu").manual_seed(pages + k)
     scores = torch.randn((B, H, pages * subs), generator=g).half()
@@ -88,3 +89,5 @@ def test_select_topk_pages_matches_torch(B, H, pages, subs, k):
     # ties go to the lower page index: the 1.5-block of row (0, 0) comes out in ascending page order
     tied = [int(p) for p, v in zip(sel[0, 0].tolist(), got_vals[0, 0].tolist()) if v == 1.5]
     assert tied == sorted(tied)
+    # ... and every row is the oracle's choice, page for page (descending score, ties to the lower page, newest page last)
+    assert np.array_equal(out.cpu().numpy(), kv4.topk_pages(scores.numpy(), subs, pages, k))
