@@ -375,6 +375,31 @@ int omni_kv4_prefill_write_at(void* qkv_f16, const void* seq_lens_i32, const voi
                               int tokens_per_block, const void* rope_cos_sin_f32, int rope_max_pos,
                               int max_position_embeddings, void* stream);
 
+/* Project extension (no reference counterpart; the nodes of a token tree, omni_decode_attention_tree_kv4):
+ * omni_kv4_prefill_write_at with the RoPE row decoupled from the slot.  rope_offsets int32 [tokens] (device), in token order:
+ * token i of sequence b is written to page / slot past_lens[b] + i, as omni_kv4_prefill_write_at does, and rotated (q and k in
+ * place) with RoPE row past_lens[b] + rope_offsets[token] (a node's depth: siblings share a position; a negative row is taken
+ * as 0, a row >= rope_max_pos as the last one).  rope_offsets[token] = i gives omni_kv4_prefill_write_at's bytes.  Every other
+ * argument, check and limit is omni_kv4_prefill_write_at's; -EINVAL also for a NULL rope_offsets. */
+int omni_kv4_prefill_write_at_pos(void* qkv_f16, const void* seq_lens_i32, const void* past_lens_i32,
+                                  const void* rope_offsets_i32, const void* padding_offsets_i32, const void* kv_pointers_i64,
+                                  int tokens, int batch, int max_blocks, int num_heads, int num_kv_heads, int head_dim,
+                                  int max_seq_len, int tokens_per_block, const void* rope_cos_sin_f32, int rope_max_pos,
+                                  int max_position_embeddings, void* stream);
+
+/* Project extension (no reference counterpart; the rollback of a tree verify step): move the KV4 rows of an accepted path to
+ * the front.  For every sequence b, kv head, K and V pool of kv_pointers (int64 [B, 2, max_blocks]) and every j < counts[b]
+ * the row at position base_lens[b] + src[b][j] is moved to position base_lens[b] + j: its 64 code bytes and its fp16 scale and
+ * zero point in the page tails, byte-exact; source and destination may lie in different pages; nothing else in any page
+ * changes.  base_lens, counts int32 [B], src int32 [B, max_rows] (device), max_rows <= 32.  Contract (not checked on the
+ * device): src[b][j] >= j and src[b] strictly increasing in j, base + src inside the block table.  A destination may be the
+ * source of another move (path 0, 2, 3: slot 2 is read for j = 1 and written for j = 2): every row of a (sequence, head, pool)
+ * is read before any is written.  src[b][j] == j stores nothing.  -EINVAL: max_rows outside [1, 32], head_dim != 128,
+ * tokens_per_block not a power of two >= 16, a NULL pointer.  batch = 0 returns 0 and launches nothing. */
+int omni_kv4_compact_rows(const void* kv_pointers_i64, const void* base_lens_i32, const void* src_i32,
+                          const void* counts_i32, int batch, int max_blocks, int tokens_per_block, int num_kv_heads,
+                          int head_dim, int max_rows, void* stream);
+
 /* Tuning hook: force the number of KV splits of omni_kv4_decode_attention (0 = heuristic). */
 void omni_kv4_decode_set_split_override(int nsplit);
 
@@ -467,6 +492,23 @@ size_t omni_decode_attention_multi_kv4_workspace_bytes(int batch, int num_heads,
 /* Project extension (no reference counterpart): tuning / test hook -- force the number of KV splits of
  * omni_decode_attention_multi_kv4 (at most 16; 0 = the planner decides).  Splits that hold no past token contribute nothing. */
 void omni_decode_attention_multi_kv4_set_split_override(int nsplit);
+/* Project extension (no reference counterpart): the tree form of omni_decode_attention_multi_kv4 -- the verify step over a
+ * token TREE (Medusa / EAGLE heads, top-k branching), 0 <= len_q <= 32 new tokens per sequence.  tree_mask uint32 [tokens]
+ * (device), one word per query token in the order of q / cu_seqlens_q: the row of token i of sequence b sees fresh key j of its
+ * own sequence iff bit j of its word is set and j < len_q (bits at or above len_q are ignored).  For a node of a tree the word
+ * holds its ancestors and itself; the chain's words (bits 0 .. i) give omni_decode_attention_multi_kv4's bits.  Every row sees
+ * the whole past; a row that sees no key at all (no bit, past 0) is written as zeros.  Every other argument, check and error is
+ * omni_decode_attention_multi_kv4's with the bound 32 on max_seqlen_q; -EINVAL also for a NULL tree_mask.  The same kernel
+ * body, split planner, workspace layout and merge; the split override above applies to both forms. */
+int omni_decode_attention_tree_kv4(void* out_f16, const void* q_f16, const void* k_new_f16, const void* v_new_f16,
+                                   int64_t q_stride, int64_t k_stride, int64_t v_stride,
+                                   const void* cu_seqlens_q_i32, const void* past_lens_i32, const void* tree_mask_u32,
+                                   const void* kv_pointers_i64, int batch, int max_blocks, int tokens_per_block,
+                                   int max_seqlen_q, int num_heads, int num_kv_heads, int head_dim, int max_past,
+                                   void* workspace, size_t workspace_bytes, void* stream);
+/* Project extension (no reference counterpart): scratch bytes for omni_decode_attention_tree_kv4 -- enough for the planner's
+ * split count and for every setting of the split override. */
+size_t omni_decode_attention_tree_kv4_workspace_bytes(int batch, int num_heads, int max_seqlen_q, int max_past);
 /* Tuning / test hook: 0 = 16 query rows per wave (16x16x32 MFMA, default), 1 = 32 rows per wave (32x32x16 MFMA), 2 = the 16-row
  * form on the 8-wave ping-pong schedule (waves 4-7 one segment behind waves 0-3; same results within the attention tolerance). */
 void omni_prefill_set_variant(int variant);

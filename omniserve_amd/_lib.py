@@ -85,6 +85,10 @@ PROTOTYPES = {
     "omni_decode_attention_multi_kv4": (_i, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp] + [_i] * 8 + [_vp, _sz, _vp]),
     "omni_decode_attention_multi_kv4_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "omni_decode_attention_multi_kv4_set_split_override": (None, [_i]),
+    "omni_decode_attention_tree_kv4": (_i, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp] + [_i] * 8 + [_vp, _sz, _vp]),
+    "omni_decode_attention_tree_kv4_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "omni_kv4_prefill_write_at_pos": (_i, [_vp, _vp, _vp, _vp, _vp, _vp] + [_i] * 8 + [_vp, _i, _i, _vp]),
+    "omni_kv4_compact_rows": (_i, [_vp, _vp, _vp, _vp] + [_i] * 6 + [_vp]),
     "omni_kv4_decode_set_split_override": (None, [_i]),
     "omni_prefill_set_variant": (None, [_i]),
     "omni_prefill_set_xcd_split": (None, [_i]),

@@ -636,3 +636,133 @@ def decode_attention_multi_kv4(q, k_new, v_new, cu_seqlens_q, past_lens, kv_poin
         _lib.current_stream())
     _lib.check(rc, what)
     return out
+
+
+# ---- tree verify: masked multi-token attention, RoPE depths, KV4 compaction --------------------------
+DECODE_TREE_MAX_Q = 32
+
+
+class DecodeTreeTooManyTokens(ValueError):
+    """decode_attention_tree_kv4 serves at most DECODE_TREE_MAX_Q new tokens (tree nodes) per sequence."""
+
+
+def tree_masks(parents):
+    """Ancestor masks and depths of a token tree.  parents: int tensor [n] or [B, n] (one tree per row), parents[..., 0] = -1 (the
+    root: the pending token) and 0 <= parents[..., i] < i behind it; n <= 32.  -> (mask int32, depth int32), parents' shape:
+    mask[i] = mask[parents[i]] | 1 << i (the node and its ancestors: the word decode_attention_tree_kv4 takes, bit 31 in the sign)
+    and depth[i] = depth[parents[i]] + 1 (the RoPE offset kv4_prefill_write_at_pos takes).  Pure tensor arithmetic on the
+    parents' device; the check of the parents reads their values."""
+    p = torch.as_tensor(parents)
+    if p.dim() not in (1, 2) or p.dtype not in (torch.int32, torch.int64) or p.shape[-1] < 1:
+        raise ValueError("tree_masks: parents must be an int32 / int64 [n] or [B, n] tensor")
+    n = p.shape[-1]
+    if n > DECODE_TREE_MAX_Q:
+        raise DecodeTreeTooManyTokens("tree_masks: %d nodes, at most %d" % (n, DECODE_TREE_MAX_Q))
+    p2 = p.reshape(-1, n).to(torch.int64)
+    idx = torch.arange(n, device=p2.device)
+    if not bool(((p2[:, 0] == -1) & ((p2[:, 1:] >= 0) & (p2[:, 1:] < idx[1:])).all(dim=1)).all()):
+        raise ValueError("tree_masks: parents[0] must be -1 and 0 <= parents[i] < i behind it")
+    mask = torch.ones_like(p2)
+    depth = torch.zeros_like(p2)
+    for i in range(1, n):
+        par = p2[:, i:i + 1]
+        mask[:, i] = mask.gather(1, par).squeeze(1) | (1 << i)
+        depth[:, i] = depth.gather(1, par).squeeze(1) + 1
+    mask = torch.where(mask >= (1 << 31), mask - (1 << 32), mask)      # bit 31 -> the sign bit of the int32 word
+    return mask.to(torch.int32).reshape(p.shape), depth.to(torch.int32).reshape(p.shape)
+
+
+def decode_attention_tree_kv4_workspace_bytes(batch, num_heads, max_seqlen_q, max_past):
+    return int(_lib.lib().omni_decode_attention_tree_kv4_workspace_bytes(int(batch), int(num_heads), int(max_seqlen_q),
+                                                                         int(max_past)))
+
+
+def decode_attention_tree_kv4(q, k_new, v_new, cu_seqlens_q, past_lens, tree_mask, kv_pointers, tokens_per_block, max_seqlen_q,
+                              max_past, workspace=None):
+    """decode_attention_multi_kv4 over a token tree, 0 - 32 new tokens per sequence: the row of token i sees the whole past and
+    the fresh key j of its own sequence iff bit j of tree_mask[token i] is set and j < len_q (tree_masks(parents): a node sees its
+    ancestors and itself; siblings do not see each other).  tree_mask: contiguous int32 [tokens] device tensor in q's token order
+    (never read on the host).  The chain's masks give decode_attention_multi_kv4's bits.  Everything else -- tensors, checks,
+    max_past, the workspace (decode_attention_tree_kv4_workspace_bytes) and the split override -- is decode_attention_multi_kv4's.
+    -> out fp16 [Lq, Hq, 128]."""
+    what = "fused_ext.decode_attention_tree_kv4"
+    if int(max_seqlen_q) > DECODE_TREE_MAX_Q:
+        raise DecodeTreeTooManyTokens("%s: max_seqlen_q = %d, at most %d new tokens per sequence"
+                                      % (what, int(max_seqlen_q), DECODE_TREE_MAX_Q))
+    _lib.require_cuda(workspace, tree_mask)
+    B, tpb = _check_paged_attention_args(what, q, k_new, v_new, cu_seqlens_q, past_lens, kv_pointers, tokens_per_block)
+    _check_lens(tree_mask, q.shape[0], what, "tree_mask")
+    if int(max_past) < 0 or int(max_past) > kv_pointers.shape[2] * tpb:
+        raise RuntimeError("%s: max_past must be non-negative and fit the block table" % what)
+    out = torch.empty((q.shape[0], q.shape[1], 128), dtype=torch.float16, device=q.device)
+    if q.shape[0] == 0 or B == 0 or int(max_seqlen_q) < 1:
+        return out
+    if workspace is None:
+        workspace = _lib.workspace(decode_attention_tree_kv4_workspace_bytes(B, q.shape[1], max_seqlen_q, max_past), q.device,
+                                   "decode_multi")
+    elif workspace.dtype != torch.uint8 or not workspace.is_contiguous():
+        raise RuntimeError("%s: workspace must be a contiguous uint8 tensor" % what)
+    rc = _lib.lib().omni_decode_attention_tree_kv4(
+        out.data_ptr(), q.data_ptr(), k_new.data_ptr(), v_new.data_ptr(), q.stride(0), k_new.stride(0), v_new.stride(0),
+        cu_seqlens_q.data_ptr(), past_lens.data_ptr(), tree_mask.data_ptr(), kv_pointers.data_ptr(), B, kv_pointers.shape[2], tpb,
+        int(max_seqlen_q), q.shape[1], k_new.shape[1], 128, int(max_past), workspace.data_ptr(), workspace.numel(),
+        _lib.current_stream())
+    _lib.check(rc, what)
+    return out
+
+
+def kv4_prefill_write_at_pos(qkv, seq_lens, past_lens, rope_offsets, padding_offset, kv_pointers, head_num, kv_head_num,
+                             max_seq_len, tokens_per_block, max_total_len, rotary_base=10000.0, rope_scale=1.0,
+                             cyclic_len=1 << 20):
+    """kv4_prefill_write_at with the RoPE row decoupled from the slot: token i of sequence b is written to page / slot
+    past_lens[b] + i and rotated (q and k in place) at RoPE row past_lens[b] + rope_offsets[token].  rope_offsets: contiguous int32
+    [tokens] device tensor (a tree node's depth, 0 <= depth <= i: tree_masks).  Same checks as kv4_prefill_write_at; the RoPE
+    table is built for max_total_len, the host's bound on max(past + len), which covers past + depth."""
+    from ..rope import rope_table
+    what = "fused_ext.kv4_prefill_write_at_pos"
+    _lib.require_cuda(qkv, seq_lens, past_lens, rope_offsets, padding_offset, kv_pointers)
+    width = (head_num + 2 * kv_head_num) * 128
+    if qkv.dtype != torch.float16 or qkv.dim() != 2 or qkv.shape[1] != width or not qkv.is_contiguous():
+        raise RuntimeError("%s: qkv must be contiguous fp16 [tokens, (Hq+2Hkv)*128]" % what)
+    B = seq_lens.shape[0]
+    _check_lens(seq_lens, B, what, "seq_lens")
+    _check_lens(past_lens, B, what, "past_lens")
+    _check_lens(rope_offsets, qkv.shape[0], what, "rope_offsets")
+    _check_lens(padding_offset, qkv.shape[0], what, "padding_offset")
+    if kv_pointers.dtype != torch.int64 or kv_pointers.dim() != 3 or kv_pointers.shape[0] != B or kv_pointers.shape[1] != 2 \
+            or not kv_pointers.is_contiguous():
+        raise RuntimeError("%s: kv_pointers must be a contiguous int64 [B,2,blocks] tensor" % what)
+    if int(max_total_len) < int(max_seq_len) or int(max_total_len) > kv_pointers.shape[2] * int(tokens_per_block):
+        raise RuntimeError("%s: max_total_len must cover the call's tokens and fit the block table" % what)
+    table = rope_table(int(max_total_len), 128, float(rotary_base), float(rope_scale), qkv.device)
+    rc = _lib.lib().omni_kv4_prefill_write_at_pos(
+        qkv.data_ptr(), seq_lens.data_ptr(), past_lens.data_ptr(), rope_offsets.data_ptr(), padding_offset.data_ptr(),
+        kv_pointers.data_ptr(), qkv.shape[0], B, kv_pointers.shape[2], int(head_num), int(kv_head_num), 128, int(max_seq_len),
+        int(tokens_per_block), table.data_ptr(), table.shape[0], int(cyclic_len), _lib.current_stream())
+    _lib.check(rc, what)
+
+
+def kv4_compact_rows(kv_pointers, base_lens, src, counts, tokens_per_block, num_kv_heads):
+    """Move the KV4 rows of an accepted tree path to the front: for every sequence b, kv head, K and V pool and j < counts[b] the
+    row (64 code bytes, fp16 scale, fp16 zero point) at position base_lens[b] + src[b, j] goes to position base_lens[b] + j,
+    byte-exact, across pages where need be; nothing else changes.  kv_pointers int64 [B, 2, blocks]; base_lens, counts int32 [B];
+    src int32 [B, max_rows], max_rows <= 32 -- device tensors, never read on the host.  Contract (not checked): src[b] strictly
+    increasing with src[b, j] >= j (a path through a tree whose nodes were written in index order), base + src inside the block
+    table.  A destination may be another move's source (path 0, 2, 3): all rows are read before any is written."""
+    what = "fused_ext.kv4_compact_rows"
+    _lib.require_cuda(kv_pointers, base_lens, src, counts)
+    if kv_pointers.dtype != torch.int64 or kv_pointers.dim() != 3 or kv_pointers.shape[1] != 2 or not kv_pointers.is_contiguous():
+        raise RuntimeError("%s: kv_pointers must be a contiguous int64 [B,2,blocks] tensor" % what)
+    B = kv_pointers.shape[0]
+    _check_lens(base_lens, B, what, "base_lens")
+    _check_lens(counts, B, what, "counts")
+    if src.dtype != torch.int32 or src.dim() != 2 or src.shape[0] != B or not src.is_contiguous():
+        raise RuntimeError("%s: src must be a contiguous int32 [B, max_rows] tensor" % what)
+    if src.shape[1] < 1 or src.shape[1] > DECODE_TREE_MAX_Q:
+        raise DecodeTreeTooManyTokens("%s: %d rows per sequence, at most %d" % (what, src.shape[1], DECODE_TREE_MAX_Q))
+    if B == 0:
+        return
+    rc = _lib.lib().omni_kv4_compact_rows(kv_pointers.data_ptr(), base_lens.data_ptr(), src.data_ptr(), counts.data_ptr(), B,
+                                          kv_pointers.shape[2], int(tokens_per_block), int(num_kv_heads), 128, src.shape[1],
+                                          _lib.current_stream())
+    _lib.check(rc, what)

@@ -21,13 +21,19 @@
 //     launch merges them in split order (a fixed order: two runs give the same bits).  nsplit = 1 normalises and stores itself.
 // The tile body (S^T = K Q^T, online softmax, O^T += V^T P^T), the tile staging of the past (packed bytes -> registers ->
 // dequant -> swizzled LDS slots) and of the fresh keys (LDS-DMA) are those of attn_prefill_paged.hip.
+//
+// Tree form (omni_decode_attention_tree_kv4, the verify step over a token TREE: Medusa / EAGLE heads, top-k branching): the
+// same kernel body with TREE = true, up to 32 new tokens per sequence.  Only the mask of the fresh tile differs: row (token i)
+// sees fresh key j iff bit j of tree_mask[token i] is set and j < len_q (the word = the node's ancestors and itself), in
+// place of the chain's j <= i.  The past tiles, their `full` fast path, the split and the merge are untouched.
 #include "attn_prefill_tile.h"
 #include "kv4_dequant.h"
 
 namespace omni {
 
 constexpr int DM_PACKED_ROW = PDH / 2;   // bytes of one key row of one head in a page
-constexpr int DM_MAX_Q = 8;              // new tokens per sequence
+constexpr int DM_MAX_Q = 8;              // new tokens per sequence (chain form)
+constexpr int DM_TREE_MAX_Q = 32;        // ... of the tree form: one mask word per token; the fresh tile holds 64 keys
 constexpr int DM_MAX_SPLITS = 16;
 // 256 CUs hold one 512-thread workgroup each (134 VGPRs): the planner aims at two rounds, which evens out ragged lengths
 constexpr int DM_SLOTS = 512;
@@ -37,10 +43,11 @@ struct DecodeMultiArgs {
   int64_t q_stride, k_stride, v_stride;     // elements between consecutive tokens
   const int* cu_q;                           // [B + 1]
   const int* past;                           // [B]
+  const uint32_t* tree_mask;                 // [tokens], tree form only: bit j = the token sees fresh key j of its sequence
   const int64_t* kv_pointers;                // [B][2][max_blocks]
   int max_blocks, tpb, tpb_log2;
   int num_heads, num_kv_heads;
-  int max_n;                                 // host bound of len_q (<= DM_MAX_Q); longer sequences are cut to it
+  int max_n;                                 // host bound of len_q (<= DM_MAX_Q, tree form DM_TREE_MAX_Q); longer sequences are cut
   int nsplit, row_groups;
   float* part_o;                             // [nsplit][B * max_n * Hq][128]
   float* part_ml;                            // [nsplit][B * max_n * Hq][2]
@@ -48,7 +55,9 @@ struct DecodeMultiArgs {
 };
 
 // (134 VGPRs, no scratch: three waves per SIMD, i.e. ONE 512-thread workgroup per CU.  Two would need <= 128 -- the staging
-//  registers of the past tile beside the accumulators and the score tile cost the six that are over, as in the paged kernel.)
+//  registers of the past tile beside the accumulators and the score tile cost the six that are over, as in the paged kernel.
+//  TREE = true: 140 VGPRs, no scratch -- the mask word is one more live register, the occupancy is the same.)
+template <bool TREE>
 __global__ __launch_bounds__(64 * PWAVES)
 void kv4_decode_multi_kernel(DecodeMultiArgs p) {
   __shared__ __attribute__((aligned(16))) uint8_t ktile0[PTILE];
@@ -93,6 +102,10 @@ void kv4_decode_multi_kernel(DecodeMultiArgs p) {
 #pragma unroll
     for (int s = 0; s < 4; ++s) qb[s] = *reinterpret_cast<const v8h*>(qp + 32 * s);
   }
+  // tree form: the row's ancestor bits among the fresh keys.  Bits >= len_q are cleared here: the fresh tile's rows >= len_q
+  // repeat the last key, and a set bit there would count it again.
+  uint32_t mword = 0u;
+  if constexpr (TREE) mword = p.tree_mask[q_begin + tok] & (len_q >= 32 ? 0xFFFFFFFFu : ((1u << len_q) - 1u));
   v4f oacc[8];
   float m_run = -1e30f, l_run = 0.0f;
 #pragma unroll
@@ -173,8 +186,9 @@ void kv4_decode_multi_kernel(DecodeMultiArgs p) {
     const int kb = cur_past ? PKT * (t_lo + t) : 0;            // first key of the tile, counted inside its own phase
     const bool next_any = t + 1 < n_tiles, next_past = t + 1 < n_past;
     const int kb_next = PKT * (t_lo + t + 1);
-    // the keys of a past tile end at `past`; a fresh key j is seen by the tokens >= j (and tok < len_q)
-    const int klim = cur_past ? past : tok + 1;
+    // the keys of a past tile end at `past`; a fresh key j is seen by the tokens >= j (and tok < len_q) -- tree form: by the
+    // rows whose mask word holds bit j (klim = 0 there: the fresh tile takes the bit test below)
+    const int klim = cur_past ? past : (TREE ? 0 : tok + 1);
     if (next_past) past_request(kb_next);
     v4f st[4];
     if (wave_on) {
@@ -213,7 +227,10 @@ void kv4_decode_multi_kernel(DecodeMultiArgs p) {
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const int key = kb + 16 * u + 4 * l4 + r;
-            const bool ok = key < klim;
+            bool ok = key < klim;
+            if constexpr (TREE) {                                  // (u is a constant: keys >= 32 of the fresh tile fold to false)
+              if (!cur_past) ok = u < 2 && ((mword >> (16 * u + 4 * l4 + r)) & 1u) != 0u;
+            }
             okv[4 * u + r] = ok;
             tmax = __builtin_fmaxf(tmax, ok ? st[u][r] : -1e30f);
           }
@@ -322,7 +339,7 @@ static size_t decode_multi_bytes(int batch, int num_heads, int max_n, int nsplit
 using namespace omni;
 
 extern "C" void omni_decode_attention_multi_kv4_set_split_override(int nsplit) {
-  // nsplit > 0: force the KV split count (tests, tuning sweeps; at most 16); 0: the planner decides
+  // nsplit > 0: force the KV split count of both forms (tests, tuning sweeps; at most 16); 0: the planner decides
   omni::g_dm_override_nsplit = nsplit > 0 ? nsplit : 0;
 }
 
@@ -333,16 +350,19 @@ extern "C" size_t omni_decode_attention_multi_kv4_workspace_bytes(int batch, int
   return decode_multi_bytes(batch, num_heads, n, DM_MAX_SPLITS);
 }
 
-extern "C" int omni_decode_attention_multi_kv4(void* out_f16, const void* q_f16, const void* k_new_f16, const void* v_new_f16,
-                                               int64_t q_stride, int64_t k_stride, int64_t v_stride,
-                                               const void* cu_seqlens_q_i32, const void* past_lens_i32,
-                                               const void* kv_pointers_i64, int batch, int max_blocks, int tokens_per_block,
-                                               int max_seqlen_q, int num_heads, int num_kv_heads, int head_dim, int max_past,
-                                               void* workspace, size_t workspace_bytes, void* stream) {
-  if (batch < 0 || max_seqlen_q < 0 || max_seqlen_q > DM_MAX_Q || max_past < 0) return OMNI_EINVAL;
+// The two entries' argument checks, plan and launches: `max_q` = the form's bound on max_seqlen_q, `tree_mask` = the tree form's
+// mask words (nullptr: the chain form).
+static int decode_multi_launch(void* out_f16, const void* q_f16, const void* k_new_f16, const void* v_new_f16,
+                               int64_t q_stride, int64_t k_stride, int64_t v_stride,
+                               const void* cu_seqlens_q_i32, const void* past_lens_i32, const void* tree_mask_u32, bool tree,
+                               const void* kv_pointers_i64, int batch, int max_blocks, int tokens_per_block,
+                               int max_seqlen_q, int max_q, int num_heads, int num_kv_heads, int head_dim, int max_past,
+                               void* workspace, size_t workspace_bytes, void* stream) {
+  if (batch < 0 || max_seqlen_q < 0 || max_seqlen_q > max_q || max_past < 0) return OMNI_EINVAL;
   if (!prefill_layout_ok(head_dim, num_heads, num_kv_heads, q_stride, k_stride, v_stride) || q_stride < 0 ||
       tokens_per_block < 16 || (tokens_per_block & (tokens_per_block - 1)) != 0 || max_blocks < 0)
     return OMNI_EINVAL;
+  if (tree && !tree_mask_u32) return OMNI_EINVAL;
   if (batch == 0 || max_seqlen_q == 0) return OMNI_OK;        // no query token: nothing to do
   if (!out_f16 || !q_f16 || !k_new_f16 || !v_new_f16 || !cu_seqlens_q_i32 || !past_lens_i32 || !kv_pointers_i64)
     return OMNI_EINVAL;
@@ -351,6 +371,7 @@ extern "C" int omni_decode_attention_multi_kv4(void* out_f16, const void* q_f16,
   a.q = (const half_t*)q_f16; a.k = (const half_t*)k_new_f16; a.v = (const half_t*)v_new_f16; a.out = (half_t*)out_f16;
   a.q_stride = q_stride; a.k_stride = k_stride; a.v_stride = v_stride;
   a.cu_q = (const int*)cu_seqlens_q_i32; a.past = (const int*)past_lens_i32;
+  a.tree_mask = (const uint32_t*)tree_mask_u32;
   a.kv_pointers = (const int64_t*)kv_pointers_i64;
   a.max_blocks = max_blocks; a.tpb = tokens_per_block;
   a.tpb_log2 = 0;
@@ -368,8 +389,41 @@ extern "C" int omni_decode_attention_multi_kv4(void* out_f16, const void* q_f16,
   a.part_o = (float*)workspace;
   a.part_ml = a.part_o + (size_t)a.nsplit * a.part_rows * PDH;
   const dim3 grid(a.nsplit, num_kv_heads * a.row_groups, batch);
-  hipLaunchKernelGGL(kv4_decode_multi_kernel, grid, dim3(64 * PWAVES), 0, (hipStream_t)stream, a);
+  if (tree)
+    hipLaunchKernelGGL(kv4_decode_multi_kernel<true>, grid, dim3(64 * PWAVES), 0, (hipStream_t)stream, a);
+  else
+    hipLaunchKernelGGL(kv4_decode_multi_kernel<false>, grid, dim3(64 * PWAVES), 0, (hipStream_t)stream, a);
   if (a.nsplit > 1)
     hipLaunchKernelGGL(kv4_decode_multi_merge_kernel, dim3((a.part_rows + 7) / 8), dim3(256), 0, (hipStream_t)stream, a);
   return omni_launch_status();
+}
+
+extern "C" int omni_decode_attention_multi_kv4(void* out_f16, const void* q_f16, const void* k_new_f16, const void* v_new_f16,
+                                               int64_t q_stride, int64_t k_stride, int64_t v_stride,
+                                               const void* cu_seqlens_q_i32, const void* past_lens_i32,
+                                               const void* kv_pointers_i64, int batch, int max_blocks, int tokens_per_block,
+                                               int max_seqlen_q, int num_heads, int num_kv_heads, int head_dim, int max_past,
+                                               void* workspace, size_t workspace_bytes, void* stream) {
+  return decode_multi_launch(out_f16, q_f16, k_new_f16, v_new_f16, q_stride, k_stride, v_stride, cu_seqlens_q_i32, past_lens_i32,
+                             nullptr, false, kv_pointers_i64, batch, max_blocks, tokens_per_block, max_seqlen_q, DM_MAX_Q,
+                             num_heads, num_kv_heads, head_dim, max_past, workspace, workspace_bytes, stream);
+}
+
+extern "C" size_t omni_decode_attention_tree_kv4_workspace_bytes(int batch, int num_heads, int max_seqlen_q, int max_past) {
+  (void)max_past;     // as omni_decode_attention_multi_kv4_workspace_bytes: every forced split count
+  if (batch < 1 || num_heads < 1 || max_seqlen_q < 1) return 0;
+  const int n = max_seqlen_q < DM_TREE_MAX_Q ? max_seqlen_q : DM_TREE_MAX_Q;
+  return decode_multi_bytes(batch, num_heads, n, DM_MAX_SPLITS);
+}
+
+extern "C" int omni_decode_attention_tree_kv4(void* out_f16, const void* q_f16, const void* k_new_f16, const void* v_new_f16,
+                                              int64_t q_stride, int64_t k_stride, int64_t v_stride,
+                                              const void* cu_seqlens_q_i32, const void* past_lens_i32,
+                                              const void* tree_mask_u32, const void* kv_pointers_i64, int batch, int max_blocks,
+                                              int tokens_per_block, int max_seqlen_q, int num_heads, int num_kv_heads,
+                                              int head_dim, int max_past, void* workspace, size_t workspace_bytes,
+                                              void* stream) {
+  return decode_multi_launch(out_f16, q_f16, k_new_f16, v_new_f16, q_stride, k_stride, v_stride, cu_seqlens_q_i32, past_lens_i32,
+                             tree_mask_u32, true, kv_pointers_i64, batch, max_blocks, tokens_per_block, max_seqlen_q,
+                             DM_TREE_MAX_Q, num_heads, num_kv_heads, head_dim, max_past, workspace, workspace_bytes, stream);
 }

@@ -91,7 +91,7 @@ __global__ __launch_bounds__(256) void kv4_prefill_write_kernel(
     half_t* __restrict__ qkv, const int* __restrict__ seq_lens, const int* __restrict__ padding_offsets,
     const int64_t* __restrict__ kv_pointers, int tokens, int max_blocks, int num_heads, int num_kv_heads,
     int max_seq_len, KvLayout lay, const float* __restrict__ rope, int rope_max_pos, int cyclic_len, FgArgs fg,
-    const float* __restrict__ kv_oq, const int* __restrict__ past_lens) {
+    const float* __restrict__ kv_oq, const int* __restrict__ past_lens, const int* __restrict__ rope_offsets) {
   constexpr int RB = KV8 ? DH : ROW_BYTES;
   const int slots_per_token = num_heads + num_kv_heads;
   const long long slot_id = (long long)blockIdx.x * 16 + (threadIdx.x >> 4);
@@ -109,6 +109,8 @@ __global__ __launch_bounds__(256) void kv4_prefill_write_kernel(
     pos += past;
     actual_len += past;
   }
+  // omni_kv4_prefill_write_at_pos (a token tree): the slot stays past + index, the RoPE row is past + rope_offsets[tok]
+  const int rope_pos = (past_lens && rope_offsets) ? max(past_lens[b] + rope_offsets[tok], 0) : pos;
   const int row_elems = (num_heads + 2 * num_kv_heads) * DH;
   half_t* row = qkv + (size_t)tok * row_elems;
   const bool is_kv = hs >= num_heads;
@@ -116,7 +118,7 @@ __global__ __launch_bounds__(256) void kv4_prefill_write_kernel(
   half_t* x = is_kv ? row + (size_t)(num_heads + hk) * DH : row + (size_t)hs * DH;
 
   // RoPE (neox): pair (i, i+64), coefficients from the host table [pos][64][2]
-  const int rp = pos < rope_max_pos ? pos : rope_max_pos - 1;
+  const int rp = rope_pos < rope_max_pos ? rope_pos : rope_max_pos - 1;
   const float* cs = rope + ((size_t)rp * (DH / 2) + 4 * l) * 2;
   const v4f cs0 = *reinterpret_cast<const v4f*>(cs);
   const v4f cs1 = *reinterpret_cast<const v4f*>(cs + 4);
@@ -224,6 +226,68 @@ __global__ __launch_bounds__(256) void kv4_prefill_write_kernel(
       sc[0] = scale_h;
       sc[hpool * lay.tpb] = zero_h;
     }
+  }
+}
+
+// ------------------------------------------------------------------------------------------
+// Compaction of an accepted tree path (project extension: the rollback of a tree verify step).  The step wrote its n nodes to the
+// slots base + 0 .. base + n - 1; the accepted path src[b][0] < src[b][1] < ... (src[b][j] >= j) must end up in base + j.
+// One 64-lane workgroup = one wave per (K or V pool, kv head, sequence) moves up to 32 rows: lane l holds bytes [32 * (l & 1),
+// + 32) of row l / 2 (64 code bytes a row), lanes 0 .. 31 also row l's fp16 scale and zero point of the page tails.
+// Hazard: a destination base + j can be the source of another move (path [0, 2, 3]: slot 2 is read for j = 1 and written for
+// j = 2).  So the wave loads ALL of its rows into registers, meets the barrier (the loads have returned: its waitcnt; and the
+// compiler moves no access across it), and only then stores.  Different workgroups touch disjoint bytes.
+// A row with src == j is not stored (it is in place); an index outside the block table is skipped (the contract -- src strictly
+// increasing, src[j] >= j, base + src inside the table -- is the caller's; this only keeps a broken one inside the tables).
+// ------------------------------------------------------------------------------------------
+constexpr int COMPACT_MAX_ROWS = 32;
+
+__global__ __launch_bounds__(64) void kv4_compact_rows_kernel(
+    const int64_t* __restrict__ kv_pointers, const int* __restrict__ base_lens, const int* __restrict__ src,
+    const int* __restrict__ counts, int max_blocks, KvLayout lay, int max_rows) {
+  const int lane = threadIdx.x;
+  const int b = blockIdx.y, pool = blockIdx.x & 1, hk = blockIdx.x >> 1;
+  const int j = lane >> 1, half = lane & 1;
+  const int count = min(counts[b], max_rows);
+  const int base = base_lens[b];
+  const int64_t* tab = kv_pointers + ((size_t)b * 2 + pool) * max_blocks;
+  const int tail2 = lay.num_kv_heads * lay.tpb;                 // fp16 elements between the scale and the zero tail
+  const int limit = max_blocks << lay.tpb_log2;                 // positions the table covers
+  const int tj = lane < COMPACT_MAX_ROWS ? lane : 0;            // row of this lane's tail pair (lanes 0 .. 31)
+
+  auto row_of = [&](int r, bool from, uint8_t*& data, half_t*& tail) -> bool {
+    if (r >= count || base < 0) return false;
+    const int s = src[(size_t)b * max_rows + r];
+    if (s <= r) return false;                                   // s == r: the row is in place, neither read nor stored
+    const int pos = base + (from ? s : r);
+    if (pos < 0 || base + s >= limit) return false;
+    uint8_t* page = reinterpret_cast<uint8_t*>(tab[pos >> lay.tpb_log2]);
+    const int prow = hk * lay.tpb + (pos & (lay.tpb - 1));
+    data = page + (size_t)prow * ROW_BYTES;
+    tail = reinterpret_cast<half_t*>(page + lay.bytes_per_seq) + prow;
+    return true;
+  };
+
+  uint4 c0 = {0u, 0u, 0u, 0u}, c1 = {0u, 0u, 0u, 0u};
+  half_t sc = (half_t)0.0f, ze = (half_t)0.0f;
+  uint8_t* data = nullptr;
+  half_t* tail = nullptr;
+  if (row_of(j, true, data, tail)) {
+    c0 = *reinterpret_cast<const uint4*>(data + 32 * half);
+    c1 = *reinterpret_cast<const uint4*>(data + 32 * half + 16);
+  }
+  if (lane < COMPACT_MAX_ROWS && row_of(tj, true, data, tail)) {
+    sc = tail[0];
+    ze = tail[tail2];
+  }
+  __syncthreads();     // every row of this (pool, head, sequence) is in registers: no store can overtake a load
+  if (row_of(j, false, data, tail)) {
+    *reinterpret_cast<uint4*>(data + 32 * half) = c0;
+    *reinterpret_cast<uint4*>(data + 32 * half + 16) = c1;
+  }
+  if (lane < COMPACT_MAX_ROWS && row_of(tj, false, data, tail)) {
+    tail[0] = sc;
+    tail[tail2] = ze;
   }
 }
 
@@ -1220,6 +1284,7 @@ extern "C" int omni_compute_padding_offsets(void* out_i32, const void* cu_seqlen
 }
 
 static int kv4_prefill_write_dense(void* qkv_f16, const void* seq_lens_i32, const void* past_lens_i32,
+                                   const void* rope_offsets_i32,
                                    const void* padding_offsets_i32, const void* kv_pointers_i64,
                                    int tokens, int batch, int max_blocks, int num_heads,
                                    int num_kv_heads, int head_dim, int max_seq_len,
@@ -1239,7 +1304,7 @@ static int kv4_prefill_write_dense(void* qkv_f16, const void* seq_lens_i32, cons
                      (const int64_t*)kv_pointers_i64, tokens, max_blocks, num_heads, num_kv_heads,
                      max_seq_len, make_layout(tokens_per_block, num_kv_heads),
                      (const float*)rope_cos_sin_f32, rope_max_pos, max_position_embeddings, FgArgs{},
-                     (const float*)nullptr, (const int*)past_lens_i32);
+                     (const float*)nullptr, (const int*)past_lens_i32, (const int*)rope_offsets_i32);
   return omni_launch_status();
 }
 
@@ -1249,7 +1314,7 @@ extern "C" int omni_kv4_prefill_write(void* qkv_f16, const void* seq_lens_i32,
                                       int num_kv_heads, int head_dim, int max_seq_len,
                                       int tokens_per_block, const void* rope_cos_sin_f32,
                                       int rope_max_pos, int max_position_embeddings, void* stream) {
-  return kv4_prefill_write_dense(qkv_f16, seq_lens_i32, nullptr, padding_offsets_i32, kv_pointers_i64, tokens, batch,
+  return kv4_prefill_write_dense(qkv_f16, seq_lens_i32, nullptr, nullptr, padding_offsets_i32, kv_pointers_i64, tokens, batch,
                                  max_blocks, num_heads, num_kv_heads, head_dim, max_seq_len, tokens_per_block,
                                  rope_cos_sin_f32, rope_max_pos, max_position_embeddings, stream);
 }
@@ -1266,9 +1331,39 @@ extern "C" int omni_kv4_prefill_write_at(void* qkv_f16, const void* seq_lens_i32
   // (the past lengths live on the device: the table must cover max(past + len), which the host side that knows them checks --
   //  fused_ext.kv4_prefill_write_at; here only what the arguments show: the table covers the call's own tokens)
   if (rope_max_pos < max_seq_len) return OMNI_EINVAL;
-  return kv4_prefill_write_dense(qkv_f16, seq_lens_i32, past_lens_i32, padding_offsets_i32, kv_pointers_i64, tokens, batch,
-                                 max_blocks, num_heads, num_kv_heads, head_dim, max_seq_len, tokens_per_block,
+  return kv4_prefill_write_dense(qkv_f16, seq_lens_i32, past_lens_i32, nullptr, padding_offsets_i32, kv_pointers_i64, tokens,
+                                 batch, max_blocks, num_heads, num_kv_heads, head_dim, max_seq_len, tokens_per_block,
                                  rope_cos_sin_f32, rope_max_pos, max_position_embeddings, stream);
+}
+
+// omni_kv4_prefill_write_at with the RoPE row decoupled from the slot (the nodes of a token tree: siblings share a position):
+// token i of sequence b goes to page / slot past_lens[b] + i and is rotated at row past_lens[b] + rope_offsets[token].
+extern "C" int omni_kv4_prefill_write_at_pos(void* qkv_f16, const void* seq_lens_i32, const void* past_lens_i32,
+                                             const void* rope_offsets_i32, const void* padding_offsets_i32,
+                                             const void* kv_pointers_i64, int tokens, int batch, int max_blocks, int num_heads,
+                                             int num_kv_heads, int head_dim, int max_seq_len, int tokens_per_block,
+                                             const void* rope_cos_sin_f32, int rope_max_pos, int max_position_embeddings,
+                                             void* stream) {
+  if (!past_lens_i32 || !rope_offsets_i32) return OMNI_EINVAL;
+  if (rope_max_pos < max_seq_len) return OMNI_EINVAL;      // (as omni_kv4_prefill_write_at)
+  return kv4_prefill_write_dense(qkv_f16, seq_lens_i32, past_lens_i32, rope_offsets_i32, padding_offsets_i32, kv_pointers_i64,
+                                 tokens, batch, max_blocks, num_heads, num_kv_heads, head_dim, max_seq_len, tokens_per_block,
+                                 rope_cos_sin_f32, rope_max_pos, max_position_embeddings, stream);
+}
+
+// Move the rows of an accepted tree path to the front of the call's slots (see kv4_compact_rows_kernel).
+extern "C" int omni_kv4_compact_rows(const void* kv_pointers_i64, const void* base_lens_i32, const void* src_i32,
+                                     const void* counts_i32, int batch, int max_blocks, int tokens_per_block, int num_kv_heads,
+                                     int head_dim, int max_rows, void* stream) {
+  if (batch < 0 || max_blocks < 1 || num_kv_heads < 1 || num_kv_heads > 32767 || head_dim != DH || max_rows < 1 ||
+      max_rows > COMPACT_MAX_ROWS || tokens_per_block < 16 || (tokens_per_block & (tokens_per_block - 1)) != 0)
+    return OMNI_EINVAL;
+  if (batch == 0) return OMNI_OK;
+  if (!kv_pointers_i64 || !base_lens_i32 || !src_i32 || !counts_i32 || batch > 65535) return OMNI_EINVAL;
+  hipLaunchKernelGGL(kv4_compact_rows_kernel, dim3(2 * num_kv_heads, batch), dim3(64), 0, (hipStream_t)stream,
+                     (const int64_t*)kv_pointers_i64, (const int*)base_lens_i32, (const int*)src_i32, (const int*)counts_i32,
+                     max_blocks, make_layout(tokens_per_block, num_kv_heads), max_rows);
+  return omni_launch_status();
 }
 
 static int fill_fg(FgArgs* fg, const void* streaming_kv_pointers_i64, const void* retrieval_head_flags_i32,
@@ -1322,13 +1417,13 @@ static int prefill_write_fg_common(
                        (half_t*)qkv_f16, (const int*)seq_lens_i32, (const int*)padding_offsets_i32,
                        (const int64_t*)retrieval_kv_pointers_i64, tokens, retrieval_blocks, num_heads, num_kv_heads,
                        max_seq_len, make_layout(tokens_per_block, num_kv_heads),
-                       (const float*)rope_cos_sin_f32, rope_max_pos, max_position_embeddings, fg, kv_oq, (const int*)nullptr);
+                       (const float*)rope_cos_sin_f32, rope_max_pos, max_position_embeddings, fg, kv_oq, (const int*)nullptr, (const int*)nullptr);
   else
     hipLaunchKernelGGL(kv4_prefill_write_kernel<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream,
                        (half_t*)qkv_f16, (const int*)seq_lens_i32, (const int*)padding_offsets_i32,
                        (const int64_t*)retrieval_kv_pointers_i64, tokens, retrieval_blocks, num_heads, num_kv_heads,
                        max_seq_len, make_layout(tokens_per_block, num_kv_heads),
-                       (const float*)rope_cos_sin_f32, rope_max_pos, max_position_embeddings, fg, kv_oq, (const int*)nullptr);
+                       (const float*)rope_cos_sin_f32, rope_max_pos, max_position_embeddings, fg, kv_oq, (const int*)nullptr, (const int*)nullptr);
   return omni_launch_status();
 }
 

@@ -131,6 +131,33 @@ def accept_lengths(draft, pred):
     return 1 + torch.cumprod(match, dim=1).sum(dim=1)
 
 
+def accept_paths(parents, tokens, pred):
+    """The accepted path per sequence through a verified token tree.  parents int [n]: one topology for the batch, parents[0] =
+    -1, parents[i] < i; tokens int64 [B, n]: the nodes' tokens (node 0 = the pending token); pred int64 [B, n]: the model's
+    token behind node i's path.  Start at node 0, which is always kept; from node c take the LOWEST-index child j with
+    tokens[b, j] == pred[b, c]; stop when there is none (a match below a rejected node is never reached).  -> (path int64
+    [B, n]: the kept nodes in order, strictly increasing, padded with -1; m int64 [B]: how many).  For chain parents m ==
+    accept_lengths(tokens, pred).  Pure tensor arithmetic (CPU or device, no host read)."""
+    B, n = tokens.shape
+    dev = tokens.device
+    par = torch.as_tensor(parents, device=dev).to(torch.int64).view(1, n)
+    idx = torch.arange(n, device=dev).view(1, n)
+    cur = torch.zeros((B,), dtype=torch.int64, device=dev)
+    alive = torch.ones((B,), dtype=torch.bool, device=dev)
+    path = torch.full((B, n), -1, dtype=torch.int64, device=dev)
+    path[:, 0] = 0
+    m = torch.ones((B,), dtype=torch.int64, device=dev)
+    for step in range(1, n):
+        want = pred.gather(1, cur.view(B, 1))
+        cand = (par == cur.view(B, 1)) & (tokens == want) & alive.view(B, 1)
+        nxt = torch.where(cand, idx, n).min(dim=1).values
+        alive = nxt < n
+        cur = torch.where(alive, nxt, cur)
+        path[:, step] = torch.where(alive, nxt, -1)
+        m = m + alive.to(torch.int64)
+    return path, m
+
+
 class DecodeRunner:
     """bs sequences with `context` cached tokens each; step() decodes one token per sequence."""
 
@@ -731,10 +758,12 @@ class DecodeRunner:
         self.tokens.copy_(torch.argmax(logits, dim=-1))
         self.lengths.add_(n)
 
-    def _extend_rows(self, n, tokens, past_max, attention):
+    def _extend_rows(self, n, tokens, past_max, attention, rope_offsets=None):
         """The decoder layers on B * n rows that continue the sequences in the KV pools (extend(), verify()): writes the rows'
         keys / values at positions lengths + i and returns the rows' final hidden states [B * n, hidden] (a view of a buffer
         the next call reuses).  `attention(q, k, v, cu, past, table, tpb, n)`: the attention over quantised past + fresh rows.
+        rope_offsets (verify_tree(): int32 [B * n], the nodes' depths): the rows still go to the slots lengths + i but are rotated
+        at lengths + rope_offsets (fused_ext.kv4_prefill_write_at_pos); None: the plain writer at an offset.
         self.lengths is left alone."""
         from .backend.fused_attention_fine_grained_dense import compute_padding_offsets
         c, B, dev = self.cfg, self.B, self.device
@@ -774,8 +803,12 @@ class DecodeRunner:
             else:
                 fused_ext.add_rms_norm_general_fuse_sum(qh, x, proj, Ly["ln1"], mB, sB, c.eps)
             Ly["qkv"].forward(qh, sB, mB, qkv)
-            fused_ext.kv4_prefill_write_at(qkv, lens, past, pad, self.block_tables[li], hq, hk, n, self.tpb, past_max + n,
-                                           c.rope_theta, 1.0, 1 << 20)
+            if rope_offsets is None:
+                fused_ext.kv4_prefill_write_at(qkv, lens, past, pad, self.block_tables[li], hq, hk, n, self.tpb, past_max + n,
+                                               c.rope_theta, 1.0, 1 << 20)
+            else:
+                fused_ext.kv4_prefill_write_at_pos(qkv, lens, past, rope_offsets, pad, self.block_tables[li], hq, hk, n,
+                                                   self.tpb, past_max + n, c.rope_theta, 1.0, 1 << 20)
             attn = attention(q, k, v, cu, past, self.block_tables[li], self.tpb, n)
             if per_chn:
                 fused_kernels.invoke_quant_fuse_sum(qa, attn.view(T, hq * d), mA, sA)
@@ -829,6 +862,55 @@ class DecodeRunner:
         self.tokens.copy_(pred.gather(1, last).squeeze(1))
         self.lengths.add_(m.to(torch.int32))
         return pred, m
+
+    def verify_tree(self, tokens, parents):
+        """verify() over a token TREE (Medusa / EAGLE heads, top-k branching, n-gram alternatives): score n = tokens.shape[1] <=
+        32 nodes per sequence in one pass over the weights.  tokens int64 [B, n]: column 0 is self.tokens (the pending token),
+        column i the token of node i; parents: n ints, ONE topology for the batch, parents[0] = -1 and 0 <= parents[i] < i
+        (checked here, on the host).  Node i is written to slot lengths + i but rotated at position lengths + depth(i)
+        (fused_ext.kv4_prefill_write_at_pos) and attends to the past and to its ancestors only
+        (fused_ext.decode_attention_tree_kv4 with fused_ext.tree_masks); then final norm, lm_head and arg-max at ALL n nodes:
+        pred[b, i] = the model's token behind node i's path.  (path, m) = accept_paths(parents, tokens, pred); every layer's K / V
+        rows of the path move from the slots lengths + path[b, j] to lengths + j (fused_ext.kv4_compact_rows), then lengths += m,
+        tokens = pred[b, path[b, m - 1]] and self.x / self.normed = that node's hidden state.  The rejected nodes' slots lie at
+        positions >= lengths, as after verify().  Eager launches.  -> (pred, path, m)."""
+        c, B = self.cfg, self.B
+        if tokens.dim() != 2 or tokens.shape[0] != B or tokens.dtype != torch.int64:
+            raise ValueError("verify_tree expects int64 [B, n] tokens")
+        n = int(tokens.shape[1])
+        if n < 1 or n > fused_ext.DECODE_TREE_MAX_Q:
+            raise ValueError("verify_tree takes 1 to %d nodes per sequence, got %d" % (fused_ext.DECODE_TREE_MAX_Q, n))
+        par = [int(p) for p in (parents.tolist() if torch.is_tensor(parents) else parents)]
+        if len(par) != n or par[0] != -1 or any(not 0 <= par[i] < i for i in range(1, n)):
+            raise ValueError("verify_tree: parents must hold n entries with parents[0] = -1 and 0 <= parents[i] < i")
+        tokens = tokens.to(self.device)
+        if not bool((tokens[:, 0] == self.tokens).all().item()):
+            raise ValueError("verify_tree: column 0 of the tokens must be the runner's pending tokens")
+        past_max = int(self.lengths.max().item())
+        if past_max + n + 1 > self.max_context:
+            raise ValueError("lengths + tree size does not fit the runner's KV pools")
+        mask1, depth1 = fused_ext.tree_masks(torch.tensor(par, dtype=torch.int64))
+        mask = mask1.repeat(B).to(self.device)
+        depth = depth1.repeat(B).to(self.device)
+
+        def attention(q, k, v, cu, past, table, tpb, n_):
+            return fused_ext.decode_attention_tree_kv4(q, k, v, cu, past, mask, table, tpb, n_, past_max)
+
+        x = self._extend_rows(n, tokens.reshape(-1), past_max, attention, rope_offsets=depth)
+        normed = torch.empty_like(x)
+        layernorm_ops.rms_norm(normed, x, self.final_norm, c.eps, False)
+        pred = torch.argmax(torch.matmul(normed, self.lm_head.t()), dim=-1).view(B, n)
+        path, m = accept_paths(par, tokens, pred)
+        src, counts = path.to(torch.int32).contiguous(), m.to(torch.int32)
+        for table in self.block_tables:
+            fused_ext.kv4_compact_rows(table, self.lengths, src, counts, self.tpb, self.kl)
+        last = path.gather(1, (m - 1).view(B, 1))
+        pick = last.view(B, 1, 1).expand(B, 1, c.hidden)
+        self.x.copy_(x.view(B, n, c.hidden).gather(1, pick).squeeze(1))
+        self.normed.copy_(normed.view(B, n, c.hidden).gather(1, pick).squeeze(1))
+        self.tokens.copy_(pred.gather(1, last).squeeze(1))
+        self.lengths.add_(counts)
+        return pred, path, m
 
     def _all_reduce(self, buf):
         if self.tp_size > 1:
