@@ -304,6 +304,20 @@ size_t omni_argmax_workspace_bytes(int rows);
 int omni_argmax_f16(void* out_i64, const void* logits_f16, int64_t row_stride, int rows, int cols, void* workspace,
                     size_t workspace_bytes, void* stream);
 
+/* Sampled decoding (replaces the torch code of omniserve/modeling/layers/sampler.py:29-50, 96-102; contract: DESIGN.md
+ * section 4.6).  logits fp16 [rows, cols] with a row stride (any alignment, cols <= 2^22, rows <= 65535); per row on the
+ * device: temperature f32, top_k i32 (<= 0: off), top_p f32 (>= 1: off), u f32 in [0, 1), and optionally probe / exclude
+ * i64 token ids (-1: none).  token_out_i64[r]: the first maximum (omni_argmax_f16's answer) for a greedy row
+ * (temperature < 1e-5, top_p < 1e-8, top_k == 1, a NaN / +inf maximum, or nothing but -inf); otherwise the token whose
+ * interval of the normalised cumulative weight contains u, over the kept set {x >= max(t_p, t_k)} less `exclude`, laid out
+ * by value descending, then index ascending.  probe_prob_out_f32[r] (nullable; needs probe): the probed token's probability
+ * under the kept set (0 if filtered out; 1 / 0 for a greedy row).  Deterministic; no host read, no allocation.
+ * workspace >= omni_sample_workspace_bytes(rows, cols). */
+size_t omni_sample_workspace_bytes(int rows, int cols);
+int omni_sample_f16(void* token_out_i64, void* probe_prob_out_f32, const void* logits_f16, int64_t row_stride, int rows,
+                    int cols, const void* temperature_f32, const void* top_k_i32, const void* top_p_f32, const void* u_f32,
+                    const void* probe_i64, const void* exclude_i64, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Embedding lookup of the decode drivers (torch.nn.Embedding upstream): out fp16 [rows, cols] = table[idx[r], :],
  * idx int64 [rows] on the device; cols % 8 == 0; ids outside [0, table_rows) leave their row untouched. */
 int omni_gather_rows_f16(void* out_f16, const void* table_f16, const void* idx_i64, int rows, int cols,

@@ -444,6 +444,54 @@ def argmax(out, logits):
     _lib.check(rc, "fused_ext.argmax")
 
 
+def _per_row(value, rows, dtype, device, name):
+    """A sampling parameter as a contiguous [rows] device tensor of `dtype` (a Python scalar is broadcast)."""
+    if not torch.is_tensor(value):
+        return torch.full((rows,), value, dtype=dtype, device=device)
+    if value.dtype != dtype or value.numel() != rows or not value.is_contiguous():
+        raise RuntimeError("sample: %s must be a contiguous %s tensor with one entry per row" %
+                           (name, str(dtype).replace("torch.", "")))
+    return value
+
+
+def sample(out, logits, temperature, top_k, top_p, u, probe=None, exclude=None, probe_prob=None):
+    """out int64 [rows] = one sampled token per row of logits fp16 [rows, cols]: temperature, then the top-p filter, then the
+    top-k filter, then the draw -- one kernel family in place of the reference sampler's torch code (omniserve/modeling/
+    layers/sampler.py:29-50, 96-102: the three HF warpers, softmax, torch.multinomial), full-vocabulary sort included.
+    temperature f32 / top_k i32 (<= 0: off) / top_p f32 (>= 1: off): per-row device tensors or Python scalars; u f32 [rows] in
+    [0, 1): the draw.  A row with temperature < 1e-5, top_p < 1e-8 or top_k == 1 (the reference's greedy test), with a NaN /
+    +inf maximum or nothing but -inf gets fused_ext.argmax's token.  probe / exclude int64 [rows] (-1: none): probe_prob f32
+    [rows] = the probed token's probability under the filtered distribution (0 if filtered out); the excluded token is left
+    out of the draw (the rejection rule of speculative sampling needs both).  Contract and tie rule: DESIGN.md section 4.6."""
+    if logits.dtype != torch.float16 or logits.dim() != 2 or logits.stride(1) != 1:
+        raise RuntimeError("sample: logits must be fp16 [rows, cols] with contiguous rows")
+    rows, cols = logits.shape
+    if out.dtype != torch.int64 or out.numel() != rows or not out.is_contiguous():
+        raise RuntimeError("sample: out must be a contiguous int64 [rows] tensor")
+    dev = logits.device
+    temperature = _per_row(temperature, rows, torch.float32, dev, "temperature")
+    top_k = _per_row(top_k, rows, torch.int32, dev, "top_k")
+    top_p = _per_row(top_p, rows, torch.float32, dev, "top_p")
+    if not torch.is_tensor(u):
+        raise RuntimeError("sample: u must be a float32 tensor with one draw per row")
+    u = _per_row(u, rows, torch.float32, dev, "u")
+    if probe_prob is not None and probe is None:
+        raise RuntimeError("sample: probe_prob needs probe")
+    if probe is not None:
+        probe = _per_row(probe, rows, torch.int64, dev, "probe")
+    if exclude is not None:
+        exclude = _per_row(exclude, rows, torch.int64, dev, "exclude")
+    if probe_prob is not None:
+        probe_prob = _per_row(probe_prob, rows, torch.float32, dev, "probe_prob")
+    _lib.require_cuda(out, logits, temperature, top_k, top_p, u, probe, exclude, probe_prob)
+    need = _lib.lib().omni_sample_workspace_bytes(rows, cols)
+    ws = _lib.workspace(need, dev, "sample")
+    rc = _lib.lib().omni_sample_f16(out.data_ptr(), _ptr(probe_prob), logits.data_ptr(), logits.stride(0), rows, cols,
+                                    temperature.data_ptr(), top_k.data_ptr(), top_p.data_ptr(), u.data_ptr(), _ptr(probe),
+                                    _ptr(exclude), ws.data_ptr(), ws.numel(), _lib.current_stream())
+    _lib.check(rc, "fused_ext.sample")
+
+
 def select_topk_pages(out, scores, subs_per_page, total_pages, k):
     """out int32 [B, Hq, k+1] <- the k best pages of [0, total_pages-1) by max-over-sub-chunks selector score (descending),
     then the newest page: one kernel for the torch view / max / topk / cat / to(int32) sequence of

@@ -62,15 +62,25 @@ class LServeDecodeRunner:
     def __init__(self, cfg: LlamaConfig, batch: int, context: int, max_new: int, device, seed=0, kv_format="kv8",
                  streaming_ratio=0.5, sink=128, local=256, budget_tokens=4096, selector_interval=4,
                  sub_chunk_per_block=4, use_graph=True, fused=True, prefetch_mb=None, ctx_sink=128, ctx_local=8192,
-                 prefetch_blocks=160, arm_o=False, defer=True, qkv_slabs=True, rowfree=True):
+                 prefetch_blocks=160, arm_o=False, defer=True, qkv_slabs=True, rowfree=True, sampling=False):
         """fused: use the opt-in fused entry points (residual add + norm + quant, silu*mul + quant) -- bit-identical to the
         reference call sequence, three launches fewer per layer.  fused=True (or 3) also takes the
         row-kernel-free forms where they apply (batch <= 16: the attention merge leaves fp16 + row maxima, gate_up runs
         with the SiLU*mul epilogue, o_proj / down_proj quantise on the fly -- runtime.py's fusion level 3 for the W8A8
         layers); fused=2 keeps the quantiser row kernels.  prefetch_mb / prefetch_blocks / arm_o / defer / qkv_slabs / rowfree: the
-        A/B switches of the step (this module reads no environment)."""
+        A/B switches of the step (this module reads no environment).  sampling=True: tokens are drawn by fused_ext.sample
+        instead of arg-max (runtime.DecodeRunner's switch: parameters start greedy, set_sampling() changes them in place)."""
         c = cfg
         self.cfg, self.B, self.device = cfg, batch, device
+        self.sampling = bool(sampling)
+        if self.sampling:      # (read by the captured steps; u is refilled outside the graphs -- see runtime.DecodeRunner)
+            self.s_temperature = torch.zeros((batch,), dtype=torch.float32, device=device)
+            self.s_top_k = torch.zeros((batch,), dtype=torch.int32, device=device)
+            self.s_top_p = torch.ones((batch,), dtype=torch.float32, device=device)
+            self.s_u = torch.zeros((batch,), dtype=torch.float32, device=device)
+            self.sample_gen = torch.Generator(device=device)
+            self.sample_gen.manual_seed(seed)
+            _lib.workspace(_lib.lib().omni_sample_workspace_bytes(batch, c.vocab), device, "sample")
         self.fused = bool(fused)
         level = 3 if fused is True else int(fused)
         # L2 weight prefetch riding on the row kernels (see omniserve_amd/runtime.py; a hint, results unaffected)
@@ -340,8 +350,7 @@ class LServeDecodeRunner:
                 if not self.fused or li == nl - 1:
                     self.x.add_(self.proj_buf)
         layernorm_ops.rms_norm(self.normed, self.x, self.final_norm, c.eps, False)
-        logits = torch.matmul(self.normed, self.lm_head.t())
-        fused_ext.argmax(self.tokens, logits)
+        self._pick(torch.matmul(self.normed, self.lm_head.t()))
 
     # ---- context stage ------------------------------------------------------------------------------------------------
     def prefill(self, tokens=None, hidden=None, seq_len=None, chunk=16384):
@@ -438,8 +447,30 @@ class LServeDecodeRunner:
             self.page_idx = [torch.zeros((B, Hq, npick), dtype=torch.int32, device=dev) for _ in self.layers]
         last = x[Lp - 1::Lp].contiguous()
         layernorm_ops.rms_norm(self.normed, last, self.final_norm, c.eps, False)
-        fused_ext.argmax(self.tokens, torch.matmul(self.normed, self.lm_head.t()))
+        self._refill_u()
+        self._pick(torch.matmul(self.normed, self.lm_head.t()))
         return x
+
+    def set_sampling(self, temperature=None, top_k=None, top_p=None, seed=None):
+        """Change the sampling parameters (a number for all sequences or one value per sequence) and / or reseed the draws;
+        written in place, so the captured steps pick them up at their next replay."""
+        if not self.sampling:
+            raise RuntimeError("set_sampling needs a runner built with sampling=True")
+        for dst, val in ((self.s_temperature, temperature), (self.s_top_k, top_k), (self.s_top_p, top_p)):
+            if val is not None:
+                dst.copy_(torch.as_tensor(val, dtype=dst.dtype).to(self.device).expand(self.B))
+        if seed is not None:
+            self.sample_gen.manual_seed(int(seed))
+
+    def _refill_u(self):
+        if self.sampling:
+            self.s_u.copy_(torch.rand((self.B,), dtype=torch.float32, device=self.device, generator=self.sample_gen))
+
+    def _pick(self, logits):
+        if self.sampling:
+            fused_ext.sample(self.tokens, logits, self.s_temperature, self.s_top_k, self.s_top_p, self.s_u)
+        else:
+            fused_ext.argmax(self.tokens, logits)
 
     def step(self):
         """Decode one token.  Two HIP graphs (with / without page selection) per history length bucket: the page
@@ -449,6 +480,7 @@ class LServeDecodeRunner:
         # decoding_attention.py:259: refresh when nothing is cached yet (first step after the context stage) or when the
         # length INCLUDING the token being generated (model_runner.py:388-400 -> max_seq_len) is a multiple of the interval
         select = self.steps_done == 0 or (self.context0 + self.steps_done + 1) % self.interval == 0
+        self._refill_u()
         if not self.use_graph:
             self._eager_step(hist, select)
             self.steps_done += 1

@@ -131,6 +131,22 @@ def accept_lengths(draft, pred):
     return 1 + torch.cumprod(match, dim=1).sum(dim=1)
 
 
+def accept_sampled(probe_prob, u_acc, drawn):
+    """The rejection rule of speculative sampling for a deterministic draft, the sampled counterpart of accept_lengths.
+    probe_prob f32 [B, n]: probe_prob[b, j] = the probability of the drafted token draft[b, j + 1] under the target's filtered
+    distribution behind draft[b, :j + 1] (column n - 1 is not read: nothing is drafted behind it); u_acc f32 [B, n]: uniforms
+    in [0, 1); drawn int64 [B, n]: drawn[b, j] = a draw from that distribution WITHOUT the drafted token (column n - 1: an
+    unrestricted draw).  Drafted token j + 1 is accepted while u_acc[b, j] < probe_prob[b, j], LEADING accepts only (an accept
+    behind a rejection does not count); m = 1 + accepts; the next pending token is drawn[b, m - 1]: at the rejection point the
+    draw without the rejected token -- for a one-hot draft distribution q the residual norm(max(p - q, 0)) is p with the
+    drafted token removed, so the output is distributed exactly as p --, behind a fully accepted draft the unrestricted draw.
+    Pure tensor arithmetic (CPU or device).  -> (m int64 [B], next int64 [B])."""
+    B, n = drawn.shape
+    ok = (u_acc[:, : n - 1] < probe_prob[:, : n - 1]).to(torch.int64)
+    m = 1 + torch.cumprod(ok, dim=1).sum(dim=1)
+    return m, drawn.gather(1, (m - 1).view(B, 1)).squeeze(1)
+
+
 def accept_paths(parents, tokens, pred):
     """The accepted path per sequence through a verified token tree.  parents int [n]: one topology for the batch, parents[0] =
     -1, parents[i] < i; tokens int64 [B, n]: the nodes' tokens (node 0 = the pending token); pred int64 [B, n]: the model's
@@ -164,7 +180,8 @@ class DecodeRunner:
     def __init__(self, cfg: LlamaConfig, batch: int, context: int, max_new: int, device, seed=0,
                  use_graph=True, fused=True, tp_rank=0, tp_size=1, tp_group=None, shard_full=False,
                  prefetch_mb=None, prefetch_blocks=160, weight_policy=1, tp_comm=None, max_fused=4, tp_l2_attn=True,
-                 l3_prefetch_down=1, qkv_slabs="auto", attn_single=True, arm_qkv=True, arm_o=True, l3_last=True):
+                 l3_prefetch_down=1, qkv_slabs="auto", attn_single=True, arm_qkv=True, arm_o=True, l3_last=True,
+                 sampling=False):
         """tp_size > 1: Megatron-style tensor parallelism (omniserve_amd/tp.py): qkv / gate_up column-parallel,
         o / down row-parallel, attention by kv head, one fp16 sum all-reduce of the [B, hidden] projection after
         o_proj and after down_proj.  shard_full=True builds the full layers from the seed and keeps this
@@ -172,7 +189,9 @@ class DecodeRunner:
         are drawn (bench: synthetic weights, no point in materialising 70B parameters per rank).
         The A/B switches of the decode step are constructor arguments (this module reads no environment): max_fused caps the
         fusion level the runner may pick; tp_l2_attn / qkv_slabs ("auto", True, False) / attn_single / arm_qkv / arm_o /
-        l3_prefetch_down (0, 1, 2) / l3_last select the forms described where they are used below."""
+        l3_prefetch_down (0, 1, 2) / l3_last select the forms described where they are used below.
+        sampling=True: every token is drawn by fused_ext.sample (temperature / top-p / top-k) instead of
+        arg-max; the parameters start at temperature 0, i.e. greedy, and set_sampling() changes them."""
         self.cfg, self.B, self.device = cfg, batch, device
         self.tp_rank, self.tp_size, self.tp_group = int(tp_rank), int(tp_size), tp_group
         # tp_comm = "peer": the decode step's collectives run on the library's own peer-mapped all-reduce (tp.PeerComm: one
@@ -362,14 +381,51 @@ class DecodeRunner:
         self.normed = torch.empty((B, c.hidden), dtype=f16, device=device)
         self.lengths = torch.full((B,), context, dtype=torch.int32, device=device)
         self.tokens = torch.randint(0, c.vocab, (B,), device=device, generator=gen)
+        # sampled decoding: per-row parameters and the draw u live in device tensors that the captured step READS, so changing
+        # them needs no re-capture; u is refilled outside the graph before each step from a generator of its own (the model's
+        # generator draws the same weights / prompts whether the runner samples or not)
+        self.sampling = bool(sampling)
+        if self.sampling:
+            self.s_temperature = torch.zeros((B,), dtype=torch.float32, device=device)
+            self.s_top_k = torch.zeros((B,), dtype=torch.int32, device=device)
+            self.s_top_p = torch.ones((B,), dtype=torch.float32, device=device)
+            self.s_u = torch.zeros((B,), dtype=torch.float32, device=device)
+            self.sample_gen = torch.Generator(device=device)
+            self.sample_gen.manual_seed(seed)
+            _lib.workspace(_lib.lib().omni_sample_workspace_bytes(8 * B, c.vocab), device, "sample")    # (verify: B * 8 rows)
         rope_table(self.max_context + 1, c.head_dim, c.rope_theta, 1.0, device)  # pre-build (capture safe)
         self.graph = None
         self.use_graph = use_graph
         self.graph_error = None       # set when a tensor-parallel graph capture failed and the runner fell back to eager
         self.steps_done = 0
 
+    def set_sampling(self, temperature=None, top_k=None, top_p=None, seed=None):
+        """Change the sampling parameters (a number for all sequences or one value per sequence) and / or reseed the draws.
+        Written into the runner's device tensors in place: a captured step picks them up at its next replay."""
+        if not self.sampling:
+            raise RuntimeError("set_sampling needs a runner built with sampling=True")
+        for dst, val in ((self.s_temperature, temperature), (self.s_top_k, top_k), (self.s_top_p, top_p)):
+            if val is not None:
+                dst.copy_(torch.as_tensor(val, dtype=dst.dtype).to(self.device).expand(self.B))
+        if seed is not None:
+            self.sample_gen.manual_seed(int(seed))
+
+    def _uniforms(self, *shape):
+        return torch.rand(shape, dtype=torch.float32, device=self.device, generator=self.sample_gen)
+
+    def _next_tokens(self, logits):
+        """self.tokens <- one token per sequence from logits fp16 [B, vocab] outside the captured step (prefill / extend):
+        arg-max, or a fresh draw on a sampling runner."""
+        if self.sampling:
+            self.s_u.copy_(self._uniforms(self.B))
+            fused_ext.sample(self.tokens, logits, self.s_temperature, self.s_top_k, self.s_top_p, self.s_u)
+        else:
+            self.tokens.copy_(torch.argmax(logits, dim=-1))
+
     def step(self):
         """Decode one token for every sequence (one HIP-graph replay once captured)."""
+        if self.sampling:
+            self.s_u.copy_(self._uniforms(self.B))      # outside the graph: the replay reads the buffer
         if not self.use_graph:
             self._eager_step()
             self.steps_done += 1
@@ -625,7 +681,9 @@ class DecodeRunner:
         else:
             layernorm_ops.rms_norm(self.normed, self.x, self.final_norm, c.eps, False)
         logits = torch.matmul(self.normed, self.lm_head.t())
-        if self.fused:
+        if self.sampling:
+            fused_ext.sample(self.tokens, logits, self.s_temperature, self.s_top_k, self.s_top_p, self.s_u)
+        elif self.fused:
             fused_ext.argmax(self.tokens, logits)      # same result as torch.argmax, 6 us instead of 47
         else:
             self.tokens.copy_(torch.argmax(logits, dim=-1))
@@ -711,8 +769,7 @@ class DecodeRunner:
         last = x.view(B, L, c.hidden)[:, L - 1]
         self.x.copy_(last)
         layernorm_ops.rms_norm(self.normed, self.x, self.final_norm, c.eps, False)
-        logits = torch.matmul(self.normed, self.lm_head.t())
-        self.tokens.copy_(torch.argmax(logits, dim=-1))
+        self._next_tokens(torch.matmul(self.normed, self.lm_head.t()))
         self.lengths.fill_(L)
 
     def _prefill_chunked(self, prompt_len, tokens, chunk):
@@ -754,8 +811,7 @@ class DecodeRunner:
         x = self._extend_rows(n, tokens, past_max, fused_ext.prefill_attention_paged_kv4)
         self.x.copy_(x.view(B, n, c.hidden)[:, n - 1])
         layernorm_ops.rms_norm(self.normed, self.x, self.final_norm, c.eps, False)
-        logits = torch.matmul(self.normed, self.lm_head.t())
-        self.tokens.copy_(torch.argmax(logits, dim=-1))
+        self._next_tokens(torch.matmul(self.normed, self.lm_head.t()))
         self.lengths.add_(n)
 
     def _extend_rows(self, n, tokens, past_max, attention, rope_offsets=None):
@@ -824,7 +880,7 @@ class DecodeRunner:
         x.add_(proj)
         return x
 
-    def verify(self, draft):
+    def verify(self, draft, sampled=None, uniforms=None):
         """One multi-token decode step (the verify step of speculative decoding): score n = draft.shape[1] <= 8 positions per
         sequence in one pass over the weights.  draft int64 [B, n]: column 0 is self.tokens (the pending token, not yet in the
         pools), columns 1 .. the drafted continuation.  extend()'s layer sequence on B * n rows with the split-KV multi-token
@@ -833,8 +889,16 @@ class DecodeRunner:
         accept_lengths(draft, pred) tokens per sequence are kept: lengths += m, tokens = pred[b, m - 1], self.x / self.normed =
         the hidden state of the last accepted position (as extend() leaves them).  Rollback: the rejected tokens' page slots
         keep their bytes; they lie at positions >= lengths, which no kernel reads and later appends overwrite.  Eager launches
-        (capturing the step in a HIP graph is the follow-up).  -> (pred, m)."""
+        (capturing the step in a HIP graph is the follow-up).  -> (pred, m).
+        sampled (default: the runner's `sampling`): the rejection rule of speculative sampling in place of "the draft equals the
+        arg-max".  ONE fused_ext.sample call over all B * n logits rows with probe = exclude = draft[b, j + 1] (-1 in the last
+        column) gives the drafted token's probability under the filtered distribution and a draw without it; m, tokens =
+        accept_sampled(probe_prob, u_acc, drawn); the state is left as above.  uniforms = (u_draw, u_acc), f32 [B, n] each:
+        the draws to use instead of fresh ones from the runner's generator (replay, tests).  -> (drawn, m)."""
         c, B = self.cfg, self.B
+        sampled = self.sampling if sampled is None else bool(sampled)
+        if sampled and not self.sampling:
+            raise RuntimeError("verify(sampled=True) needs a runner built with sampling=True")
         if draft.dim() != 2 or draft.shape[0] != B or draft.dtype != torch.int64:
             raise ValueError("verify expects an int64 [B, n] draft")
         n = int(draft.shape[1])
@@ -853,8 +917,20 @@ class DecodeRunner:
         x = self._extend_rows(n, draft.reshape(-1), past_max, attention)
         normed = torch.empty_like(x)
         layernorm_ops.rms_norm(normed, x, self.final_norm, c.eps, False)
-        pred = torch.argmax(torch.matmul(normed, self.lm_head.t()), dim=-1).view(B, n)
-        m = accept_lengths(draft, pred)
+        logits = torch.matmul(normed, self.lm_head.t())
+        if sampled:
+            u_draw, u_acc = uniforms if uniforms is not None else self._uniforms(2, B, n)
+            guess = torch.cat([draft[:, 1:], torch.full((B, 1), -1, dtype=torch.int64, device=self.device)], dim=1).reshape(-1)
+            pred = torch.empty((B * n,), dtype=torch.int64, device=self.device)
+            prob = torch.empty((B * n,), dtype=torch.float32, device=self.device)
+            fused_ext.sample(pred, logits, self.s_temperature.repeat_interleave(n), self.s_top_k.repeat_interleave(n),
+                             self.s_top_p.repeat_interleave(n), u_draw.to(self.device).reshape(-1).contiguous(),
+                             probe=guess, exclude=guess, probe_prob=prob)
+            pred = pred.view(B, n)
+            m, _ = accept_sampled(prob.view(B, n), u_acc.to(self.device).view(B, n), pred)
+        else:
+            pred = torch.argmax(logits, dim=-1).view(B, n)
+            m = accept_lengths(draft, pred)
         last = (m - 1).view(B, 1)
         pick = last.view(B, 1, 1).expand(B, 1, c.hidden)
         self.x.copy_(x.view(B, n, c.hidden).gather(1, pick).squeeze(1))
@@ -875,6 +951,9 @@ class DecodeRunner:
         tokens = pred[b, path[b, m - 1]] and self.x / self.normed = that node's hidden state.  The rejected nodes' slots lie at
         positions >= lengths, as after verify().  Eager launches.  -> (pred, path, m)."""
         c, B = self.cfg, self.B
+        if self.sampling:
+            raise NotImplementedError("verify_tree on a sampling runner: multi-branch rejection sampling is not built; the tree "
+                                      "step is greedy only (use verify() for sampled speculative decoding)")
         if tokens.dim() != 2 or tokens.shape[0] != B or tokens.dtype != torch.int64:
             raise ValueError("verify_tree expects int64 [B, n] tokens")
         n = int(tokens.shape[1])
