@@ -553,22 +553,19 @@ def _check_lens(t, n, what, name):
         raise RuntimeError("%s: %s must be a contiguous int32 [%d] tensor" % (what, name, n))
 
 
-def kv4_prefill_write_at(qkv, seq_lens, past_lens, padding_offset, kv_pointers, head_num, kv_head_num, max_seq_len,
-                         tokens_per_block, max_total_len, rotary_base=10000.0, rope_scale=1.0, cyclic_len=1 << 20):
-    """apply_bias_rope_update_kv_cache (dense KV4 + zeros) for tokens that continue a sequence: token i of sequence b is
-    position past_lens[b] + i (RoPE row, page, slot).  qkv fp16 [tokens, (Hq+2Hkv)*128] (q and k rotated in place), seq_lens /
-    past_lens int32 [B] on the device, padding_offset = compute_padding_offsets(cu_seqlens, max_seq_len, tokens).
-    max_total_len: the host's bound on max(past + len) -- the RoPE table is built for it (the lengths themselves stay on the
-    device).  Same page bytes as the plain writer would leave for the same positions."""
+def _kv4_prefill_write(what, qkv, seq_lens, past_lens, rope_offsets, padding_offset, kv_pointers, head_num, kv_head_num,
+                       max_seq_len, tokens_per_block, max_total_len, rotary_base, rope_scale, cyclic_len):
+    """kv4_prefill_write_at (rope_offsets None) and kv4_prefill_write_at_pos: the checks, the RoPE table and the call."""
     from ..rope import rope_table
-    what = "fused_ext.kv4_prefill_write_at"
-    _lib.require_cuda(qkv, seq_lens, past_lens, padding_offset, kv_pointers)
+    _lib.require_cuda(qkv, seq_lens, past_lens, rope_offsets, padding_offset, kv_pointers)
     width = (head_num + 2 * kv_head_num) * 128
     if qkv.dtype != torch.float16 or qkv.dim() != 2 or qkv.shape[1] != width or not qkv.is_contiguous():
         raise RuntimeError("%s: qkv must be contiguous fp16 [tokens, (Hq+2Hkv)*128]" % what)
     B = seq_lens.shape[0]
     _check_lens(seq_lens, B, what, "seq_lens")
     _check_lens(past_lens, B, what, "past_lens")
+    if rope_offsets is not None:
+        _check_lens(rope_offsets, qkv.shape[0], what, "rope_offsets")
     _check_lens(padding_offset, qkv.shape[0], what, "padding_offset")
     if kv_pointers.dtype != torch.int64 or kv_pointers.dim() != 3 or kv_pointers.shape[0] != B or kv_pointers.shape[1] != 2 \
             or not kv_pointers.is_contiguous():
@@ -576,11 +573,26 @@ def kv4_prefill_write_at(qkv, seq_lens, past_lens, padding_offset, kv_pointers, 
     if int(max_total_len) < int(max_seq_len) or int(max_total_len) > kv_pointers.shape[2] * int(tokens_per_block):
         raise RuntimeError("%s: max_total_len must cover the call's tokens and fit the block table" % what)
     table = rope_table(int(max_total_len), 128, float(rotary_base), float(rope_scale), qkv.device)
-    rc = _lib.lib().omni_kv4_prefill_write_at(
-        qkv.data_ptr(), seq_lens.data_ptr(), past_lens.data_ptr(), padding_offset.data_ptr(), kv_pointers.data_ptr(),
-        qkv.shape[0], B, kv_pointers.shape[2], int(head_num), int(kv_head_num), 128, int(max_seq_len),
-        int(tokens_per_block), table.data_ptr(), table.shape[0], int(cyclic_len), _lib.current_stream())
+    head = (qkv.data_ptr(), seq_lens.data_ptr(), past_lens.data_ptr())
+    tail = (padding_offset.data_ptr(), kv_pointers.data_ptr(), qkv.shape[0], B, kv_pointers.shape[2], int(head_num),
+            int(kv_head_num), 128, int(max_seq_len), int(tokens_per_block), table.data_ptr(), table.shape[0], int(cyclic_len),
+            _lib.current_stream())
+    if rope_offsets is None:
+        rc = _lib.lib().omni_kv4_prefill_write_at(*head, *tail)
+    else:
+        rc = _lib.lib().omni_kv4_prefill_write_at_pos(*head, rope_offsets.data_ptr(), *tail)
     _lib.check(rc, what)
+
+
+def kv4_prefill_write_at(qkv, seq_lens, past_lens, padding_offset, kv_pointers, head_num, kv_head_num, max_seq_len,
+                         tokens_per_block, max_total_len, rotary_base=10000.0, rope_scale=1.0, cyclic_len=1 << 20):
+    """apply_bias_rope_update_kv_cache (dense KV4 + zeros) for tokens that continue a sequence: token i of sequence b is
+    position past_lens[b] + i (RoPE row, page, slot).  qkv fp16 [tokens, (Hq+2Hkv)*128] (q and k rotated in place), seq_lens /
+    past_lens int32 [B] on the device, padding_offset = compute_padding_offsets(cu_seqlens, max_seq_len, tokens).
+    max_total_len: the host's bound on max(past + len) -- the RoPE table is built for it (the lengths themselves stay on the
+    device).  Same page bytes as the plain writer would leave for the same positions."""
+    _kv4_prefill_write("fused_ext.kv4_prefill_write_at", qkv, seq_lens, past_lens, None, padding_offset, kv_pointers, head_num,
+                       kv_head_num, max_seq_len, tokens_per_block, max_total_len, rotary_base, rope_scale, cyclic_len)
 
 
 def _check_paged_attention_args(what, q, k_new, v_new, cu_seqlens_q, past_lens, kv_pointers, tokens_per_block):
@@ -648,9 +660,45 @@ def decode_attention_multi_kv4_set_split_override(nsplit):
     _lib.lib().omni_decode_attention_multi_kv4_set_split_override(int(nsplit))
 
 
-def decode_attention_multi_kv4_workspace_bytes(batch, num_heads, max_seqlen_q, max_past):
-    return int(_lib.lib().omni_decode_attention_multi_kv4_workspace_bytes(int(batch), int(num_heads), int(max_seqlen_q),
-                                                                          int(max_past)))
+def _workspace_bytes_of(name):
+    def workspace_bytes(batch, num_heads, max_seqlen_q, max_past):
+        size = getattr(_lib.lib(), "omni_%s_workspace_bytes" % name)
+        return int(size(int(batch), int(num_heads), int(max_seqlen_q), int(max_past)))
+    return workspace_bytes
+
+
+decode_attention_multi_kv4_workspace_bytes = _workspace_bytes_of("decode_attention_multi_kv4")
+
+
+def _decode_attention_multi(name, limit, too_many, q, k_new, v_new, cu_seqlens_q, past_lens, tree_mask, kv_pointers,
+                            tokens_per_block, max_seqlen_q, max_past, workspace):
+    """decode_attention_multi_kv4 (tree_mask None: the chain entry) and decode_attention_tree_kv4: the checks, the workspace
+    and the call.  name: the public function's, which is also the C entry's behind "omni_"; limit / too_many: its token limit
+    and the exception past it."""
+    what = "fused_ext." + name
+    if int(max_seqlen_q) > limit:
+        raise too_many("%s: max_seqlen_q = %d, at most %d new tokens per sequence" % (what, int(max_seqlen_q), limit))
+    _lib.require_cuda(workspace, tree_mask)
+    B, tpb = _check_paged_attention_args(what, q, k_new, v_new, cu_seqlens_q, past_lens, kv_pointers, tokens_per_block)
+    if tree_mask is not None:
+        _check_lens(tree_mask, q.shape[0], what, "tree_mask")
+    if int(max_past) < 0 or int(max_past) > kv_pointers.shape[2] * tpb:
+        raise RuntimeError("%s: max_past must be non-negative and fit the block table" % what)
+    out = torch.empty((q.shape[0], q.shape[1], 128), dtype=torch.float16, device=q.device)
+    if q.shape[0] == 0 or B == 0 or int(max_seqlen_q) < 1:
+        return out
+    if workspace is None:
+        workspace = _lib.workspace(_workspace_bytes_of(name)(B, q.shape[1], max_seqlen_q, max_past), q.device,
+                                   "decode_multi")
+    elif workspace.dtype != torch.uint8 or not workspace.is_contiguous():
+        raise RuntimeError("%s: workspace must be a contiguous uint8 tensor" % what)
+    rc = getattr(_lib.lib(), "omni_" + name)(
+        out.data_ptr(), q.data_ptr(), k_new.data_ptr(), v_new.data_ptr(), q.stride(0), k_new.stride(0), v_new.stride(0),
+        cu_seqlens_q.data_ptr(), past_lens.data_ptr(), *(() if tree_mask is None else (tree_mask.data_ptr(),)),
+        kv_pointers.data_ptr(), B, kv_pointers.shape[2], tpb, int(max_seqlen_q), q.shape[1], k_new.shape[1], 128, int(max_past),
+        workspace.data_ptr(), workspace.numel(), _lib.current_stream())
+    _lib.check(rc, what)
+    return out
 
 
 def decode_attention_multi_kv4(q, k_new, v_new, cu_seqlens_q, past_lens, kv_pointers, tokens_per_block, max_seqlen_q, max_past,
@@ -661,29 +709,8 @@ def decode_attention_multi_kv4(q, k_new, v_new, cu_seqlens_q, past_lens, kv_poin
     max_past bounds past_lens (the host's numbers: the lengths stay on the device).  workspace: uint8 device tensor of at
     least decode_attention_multi_kv4_workspace_bytes(...) bytes, allocated (and kept) here when None.
     -> out fp16 [Lq, Hq, 128]."""
-    what = "fused_ext.decode_attention_multi_kv4"
-    if int(max_seqlen_q) > DECODE_MULTI_MAX_Q:
-        raise DecodeMultiTooManyTokens("%s: max_seqlen_q = %d, at most %d new tokens per sequence"
-                                       % (what, int(max_seqlen_q), DECODE_MULTI_MAX_Q))
-    _lib.require_cuda(workspace)
-    B, tpb = _check_paged_attention_args(what, q, k_new, v_new, cu_seqlens_q, past_lens, kv_pointers, tokens_per_block)
-    if int(max_past) < 0 or int(max_past) > kv_pointers.shape[2] * tpb:
-        raise RuntimeError("%s: max_past must be non-negative and fit the block table" % what)
-    out = torch.empty((q.shape[0], q.shape[1], 128), dtype=torch.float16, device=q.device)
-    if q.shape[0] == 0 or B == 0 or int(max_seqlen_q) < 1:
-        return out
-    if workspace is None:
-        workspace = _lib.workspace(decode_attention_multi_kv4_workspace_bytes(B, q.shape[1], max_seqlen_q, max_past), q.device,
-                                   "decode_multi")
-    elif workspace.dtype != torch.uint8 or not workspace.is_contiguous():
-        raise RuntimeError("%s: workspace must be a contiguous uint8 tensor" % what)
-    rc = _lib.lib().omni_decode_attention_multi_kv4(
-        out.data_ptr(), q.data_ptr(), k_new.data_ptr(), v_new.data_ptr(), q.stride(0), k_new.stride(0), v_new.stride(0),
-        cu_seqlens_q.data_ptr(), past_lens.data_ptr(), kv_pointers.data_ptr(), B, kv_pointers.shape[2], tpb,
-        int(max_seqlen_q), q.shape[1], k_new.shape[1], 128, int(max_past), workspace.data_ptr(), workspace.numel(),
-        _lib.current_stream())
-    _lib.check(rc, what)
-    return out
+    return _decode_attention_multi("decode_attention_multi_kv4", DECODE_MULTI_MAX_Q, DecodeMultiTooManyTokens, q, k_new, v_new,
+                                   cu_seqlens_q, past_lens, None, kv_pointers, tokens_per_block, max_seqlen_q, max_past, workspace)
 
 
 # ---- tree verify: masked multi-token attention, RoPE depths, KV4 compaction (DESIGN.md section 4.5c) --------------------------
@@ -720,9 +747,7 @@ def tree_masks(parents):
     return mask.to(torch.int32).reshape(p.shape), depth.to(torch.int32).reshape(p.shape)
 
 
-def decode_attention_tree_kv4_workspace_bytes(batch, num_heads, max_seqlen_q, max_past):
-    return int(_lib.lib().omni_decode_attention_tree_kv4_workspace_bytes(int(batch), int(num_heads), int(max_seqlen_q),
-                                                                         int(max_past)))
+decode_attention_tree_kv4_workspace_bytes = _workspace_bytes_of("decode_attention_tree_kv4")
 
 
 def decode_attention_tree_kv4(q, k_new, v_new, cu_seqlens_q, past_lens, tree_mask, kv_pointers, tokens_per_block, max_seqlen_q,
@@ -733,30 +758,11 @@ def decode_attention_tree_kv4(q, k_new, v_new, cu_seqlens_q, past_lens, tree_mas
     (never read on the host).  The chain's masks give decode_attention_multi_kv4's bits.  Everything else -- tensors, checks,
     max_past, the workspace (decode_attention_tree_kv4_workspace_bytes) and the split override -- is decode_attention_multi_kv4's.
     -> out fp16 [Lq, Hq, 128]."""
-    what = "fused_ext.decode_attention_tree_kv4"
-    if int(max_seqlen_q) > DECODE_TREE_MAX_Q:
-        raise DecodeTreeTooManyTokens("%s: max_seqlen_q = %d, at most %d new tokens per sequence"
-                                      % (what, int(max_seqlen_q), DECODE_TREE_MAX_Q))
-    _lib.require_cuda(workspace, tree_mask)
-    B, tpb = _check_paged_attention_args(what, q, k_new, v_new, cu_seqlens_q, past_lens, kv_pointers, tokens_per_block)
-    _check_lens(tree_mask, q.shape[0], what, "tree_mask")
-    if int(max_past) < 0 or int(max_past) > kv_pointers.shape[2] * tpb:
-        raise RuntimeError("%s: max_past must be non-negative and fit the block table" % what)
-    out = torch.empty((q.shape[0], q.shape[1], 128), dtype=torch.float16, device=q.device)
-    if q.shape[0] == 0 or B == 0 or int(max_seqlen_q) < 1:
-        return out
-    if workspace is None:
-        workspace = _lib.workspace(decode_attention_tree_kv4_workspace_bytes(B, q.shape[1], max_seqlen_q, max_past), q.device,
-                                   "decode_multi")
-    elif workspace.dtype != torch.uint8 or not workspace.is_contiguous():
-        raise RuntimeError("%s: workspace must be a contiguous uint8 tensor" % what)
-    rc = _lib.lib().omni_decode_attention_tree_kv4(
-        out.data_ptr(), q.data_ptr(), k_new.data_ptr(), v_new.data_ptr(), q.stride(0), k_new.stride(0), v_new.stride(0),
-        cu_seqlens_q.data_ptr(), past_lens.data_ptr(), tree_mask.data_ptr(), kv_pointers.data_ptr(), B, kv_pointers.shape[2], tpb,
-        int(max_seqlen_q), q.shape[1], k_new.shape[1], 128, int(max_past), workspace.data_ptr(), workspace.numel(),
-        _lib.current_stream())
-    _lib.check(rc, what)
-    return out
+    if tree_mask is None:
+        raise RuntimeError("fused_ext.decode_attention_tree_kv4: tree_mask must be a contiguous int32 [tokens] tensor")
+    return _decode_attention_multi("decode_attention_tree_kv4", DECODE_TREE_MAX_Q, DecodeTreeTooManyTokens, q, k_new, v_new,
+                                   cu_seqlens_q, past_lens, tree_mask, kv_pointers, tokens_per_block, max_seqlen_q, max_past,
+                                   workspace)
 
 
 def kv4_prefill_write_at_pos(qkv, seq_lens, past_lens, rope_offsets, padding_offset, kv_pointers, head_num, kv_head_num,
@@ -766,28 +772,10 @@ def kv4_prefill_write_at_pos(qkv, seq_lens, past_lens, rope_offsets, padding_off
     past_lens[b] + i and rotated (q and k in place) at RoPE row past_lens[b] + rope_offsets[token].  rope_offsets: contiguous int32
     [tokens] device tensor (a tree node's depth, 0 <= depth <= i: tree_masks).  Same checks as kv4_prefill_write_at; the RoPE
     table is built for max_total_len, the host's bound on max(past + len), which covers past + depth."""
-    from ..rope import rope_table
-    what = "fused_ext.kv4_prefill_write_at_pos"
-    _lib.require_cuda(qkv, seq_lens, past_lens, rope_offsets, padding_offset, kv_pointers)
-    width = (head_num + 2 * kv_head_num) * 128
-    if qkv.dtype != torch.float16 or qkv.dim() != 2 or qkv.shape[1] != width or not qkv.is_contiguous():
-        raise RuntimeError("%s: qkv must be contiguous fp16 [tokens, (Hq+2Hkv)*128]" % what)
-    B = seq_lens.shape[0]
-    _check_lens(seq_lens, B, what, "seq_lens")
-    _check_lens(past_lens, B, what, "past_lens")
-    _check_lens(rope_offsets, qkv.shape[0], what, "rope_offsets")
-    _check_lens(padding_offset, qkv.shape[0], what, "padding_offset")
-    if kv_pointers.dtype != torch.int64 or kv_pointers.dim() != 3 or kv_pointers.shape[0] != B or kv_pointers.shape[1] != 2 \
-            or not kv_pointers.is_contiguous():
-        raise RuntimeError("%s: kv_pointers must be a contiguous int64 [B,2,blocks] tensor" % what)
-    if int(max_total_len) < int(max_seq_len) or int(max_total_len) > kv_pointers.shape[2] * int(tokens_per_block):
-        raise RuntimeError("%s: max_total_len must cover the call's tokens and fit the block table" % what)
-    table = rope_table(int(max_total_len), 128, float(rotary_base), float(rope_scale), qkv.device)
-    rc = _lib.lib().omni_kv4_prefill_write_at_pos(
-        qkv.data_ptr(), seq_lens.data_ptr(), past_lens.data_ptr(), rope_offsets.data_ptr(), padding_offset.data_ptr(),
-        kv_pointers.data_ptr(), qkv.shape[0], B, kv_pointers.shape[2], int(head_num), int(kv_head_num), 128, int(max_seq_len),
-        int(tokens_per_block), table.data_ptr(), table.shape[0], int(cyclic_len), _lib.current_stream())
-    _lib.check(rc, what)
+    if rope_offsets is None:
+        raise RuntimeError("fused_ext.kv4_prefill_write_at_pos: rope_offsets must be a contiguous int32 [tokens] tensor")
+    _kv4_prefill_write("fused_ext.kv4_prefill_write_at_pos", qkv, seq_lens, past_lens, rope_offsets, padding_offset, kv_pointers,
+                       head_num, kv_head_num, max_seq_len, tokens_per_block, max_total_len, rotary_base, rope_scale, cyclic_len)
 
 
 def kv4_compact_rows(kv_pointers, base_lens, src, counts, tokens_per_block, num_kv_heads):

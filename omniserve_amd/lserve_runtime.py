@@ -25,7 +25,7 @@ from .backend import (activation_ops, fused_attention_ctx_pool, fused_attention_
                       fused_attention_per_tensor_sparse, fused_attention_selector, fused_ext, fused_kernels, layernorm_ops,
                       prefill_attn, qgemm_w8a8)
 from .rope import rope_table
-from .runtime import LlamaConfig
+from .runtime import LlamaConfig, SamplingState
 from . import _lib
 
 
@@ -56,7 +56,7 @@ class W8A8Linear:
         return self.weight.numel()
 
 
-class LServeDecodeRunner:
+class LServeDecodeRunner(SamplingState):
     """One sequence per batch entry with `context` cached tokens; step() decodes one token per sequence."""
 
     def __init__(self, cfg: LlamaConfig, batch: int, context: int, max_new: int, device, seed=0, kv_format="kv8",
@@ -72,14 +72,8 @@ class LServeDecodeRunner:
         instead of arg-max (runtime.DecodeRunner's switch: parameters start greedy, set_sampling() changes them in place)."""
         c = cfg
         self.cfg, self.B, self.device = cfg, batch, device
-        self.sampling = bool(sampling)
-        if self.sampling:      # (read by the captured steps; u is refilled outside the graphs -- see runtime.DecodeRunner)
-            self.s_temperature = torch.zeros((batch,), dtype=torch.float32, device=device)
-            self.s_top_k = torch.zeros((batch,), dtype=torch.int32, device=device)
-            self.s_top_p = torch.ones((batch,), dtype=torch.float32, device=device)
-            self.s_u = torch.zeros((batch,), dtype=torch.float32, device=device)
-            self.sample_gen = torch.Generator(device=device)
-            self.sample_gen.manual_seed(seed)
+        self._init_sampling(sampling, batch, device, seed)      # (read by the captured steps; u is refilled outside the graphs)
+        if self.sampling:
             _lib.workspace(_lib.lib().omni_sample_workspace_bytes(batch, c.vocab), device, "sample")
         self.fused = bool(fused)
         level = 3 if fused is True else int(fused)
@@ -450,27 +444,6 @@ class LServeDecodeRunner:
         self._refill_u()
         self._pick(torch.matmul(self.normed, self.lm_head.t()))
         return x
-
-    def set_sampling(self, temperature=None, top_k=None, top_p=None, seed=None):
-        """Change the sampling parameters (a number for all sequences or one value per sequence) and / or reseed the draws;
-        written in place, so the captured steps pick them up at their next replay."""
-        if not self.sampling:
-            raise RuntimeError("set_sampling needs a runner built with sampling=True")
-        for dst, val in ((self.s_temperature, temperature), (self.s_top_k, top_k), (self.s_top_p, top_p)):
-            if val is not None:
-                dst.copy_(torch.as_tensor(val, dtype=dst.dtype).to(self.device).expand(self.B))
-        if seed is not None:
-            self.sample_gen.manual_seed(int(seed))
-
-    def _refill_u(self):
-        if self.sampling:
-            self.s_u.copy_(torch.rand((self.B,), dtype=torch.float32, device=self.device, generator=self.sample_gen))
-
-    def _pick(self, logits):
-        if self.sampling:
-            fused_ext.sample(self.tokens, logits, self.s_temperature, self.s_top_k, self.s_top_p, self.s_u)
-        else:
-            fused_ext.argmax(self.tokens, logits)
 
     def step(self):
         """Decode one token.  Two HIP graphs (with / without page selection) per history length bucket: the page

@@ -19,8 +19,8 @@ import dataclasses
 
 import torch
 
-from .backend import (activation_ops, fused_attention_pure_dense, fused_ext, fused_kernels, layernorm_ops,
-                      qgemm_w4a8_per_chn, qgemm_w4a8_per_group)
+from .backend import (activation_ops, fused_attention_fine_grained_dense, fused_attention_pure_dense, fused_ext, fused_kernels,
+                      layernorm_ops, qgemm_w4a8_per_chn, qgemm_w4a8_per_group)
 from .rope import rope_table
 from . import _lib
 
@@ -174,7 +174,54 @@ def accept_paths(parents, tokens, pred):
     return path, m
 
 
-class DecodeRunner:
+class SamplingState:
+    """Sampled decoding's state and its two operations, for DecodeRunner and lserve_runtime.LServeDecodeRunner (a mixin: the
+    runners keep the attributes).  The per-row parameters and the draw u live in device tensors that a captured step READS, so
+    changing them needs no re-capture; u is refilled outside the graph before each step from a generator of its own (the
+    model's generator draws the same weights / prompts whether the runner samples or not).  Needs self.tokens."""
+
+    def _init_sampling(self, sampling, batch, device, seed):
+        """The parameters start at temperature 0, i.e. greedy.  (The sampler's workspace is the runner's to pre-size.)"""
+        self.sampling = bool(sampling)
+        if self.sampling:
+            self.s_temperature = torch.zeros((batch,), dtype=torch.float32, device=device)
+            self.s_top_k = torch.zeros((batch,), dtype=torch.int32, device=device)
+            self.s_top_p = torch.ones((batch,), dtype=torch.float32, device=device)
+            self.s_u = torch.zeros((batch,), dtype=torch.float32, device=device)
+            self.sample_gen = torch.Generator(device=device)
+            self.sample_gen.manual_seed(seed)
+
+    def set_sampling(self, temperature=None, top_k=None, top_p=None, seed=None):
+        """Change the sampling parameters (a number for all sequences or one value per sequence) and / or reseed the draws.
+        Written into the runner's device tensors in place: a captured step picks them up at its next replay."""
+        if not self.sampling:
+            raise RuntimeError("set_sampling needs a runner built with sampling=True")
+        for dst, val in ((self.s_temperature, temperature), (self.s_top_k, top_k), (self.s_top_p, top_p)):
+            if val is not None:
+                dst.copy_(torch.as_tensor(val, dtype=dst.dtype).to(dst.device).expand(dst.shape))
+        if seed is not None:
+            self.sample_gen.manual_seed(int(seed))
+
+    def _uniforms(self, *shape):
+        return torch.rand(shape, dtype=torch.float32, device=self.s_u.device, generator=self.sample_gen)
+
+    def _refill_u(self):
+        """s_u <- one fresh draw per sequence (nothing on a greedy runner).  Never inside a capture: the replay reads s_u."""
+        if self.sampling:
+            self.s_u.copy_(self._uniforms(self.s_u.shape[0]))
+
+    def _pick(self, logits, fused_argmax=True):
+        """self.tokens <- one token per row of logits fp16 [B, vocab]: drawn with s_u, or on a greedy runner the arg-max
+        (fused_ext.argmax, or torch's with fused_argmax=False: same result)."""
+        if self.sampling:
+            fused_ext.sample(self.tokens, logits, self.s_temperature, self.s_top_k, self.s_top_p, self.s_u)
+        elif fused_argmax:
+            fused_ext.argmax(self.tokens, logits)
+        else:
+            self.tokens.copy_(torch.argmax(logits, dim=-1))
+
+
+class DecodeRunner(SamplingState):
     """bs sequences with `context` cached tokens each; step() decodes one token per sequence."""
 
     def __init__(self, cfg: LlamaConfig, batch: int, context: int, max_new: int, device, seed=0,
@@ -381,51 +428,19 @@ class DecodeRunner:
         self.normed = torch.empty((B, c.hidden), dtype=f16, device=device)
         self.lengths = torch.full((B,), context, dtype=torch.int32, device=device)
         self.tokens = torch.randint(0, c.vocab, (B,), device=device, generator=gen)
-        # sampled decoding: per-row parameters and the draw u live in device tensors that the captured step READS, so changing
-        # them needs no re-capture; u is refilled outside the graph before each step from a generator of its own (the model's
-        # generator draws the same weights / prompts whether the runner samples or not)
-        self.sampling = bool(sampling)
+        self._init_sampling(sampling, B, device, seed)
         if self.sampling:
-            self.s_temperature = torch.zeros((B,), dtype=torch.float32, device=device)
-            self.s_top_k = torch.zeros((B,), dtype=torch.int32, device=device)
-            self.s_top_p = torch.ones((B,), dtype=torch.float32, device=device)
-            self.s_u = torch.zeros((B,), dtype=torch.float32, device=device)
-            self.sample_gen = torch.Generator(device=device)
-            self.sample_gen.manual_seed(seed)
             _lib.workspace(_lib.lib().omni_sample_workspace_bytes(8 * B, c.vocab), device, "sample")    # (verify: B * 8 rows)
+        self._prefill_bufs = None     # the context stage's activation buffers (_context_bufs)
         rope_table(self.max_context + 1, c.head_dim, c.rope_theta, 1.0, device)  # pre-build (capture safe)
         self.graph = None
         self.use_graph = use_graph
         self.graph_error = None       # set when a tensor-parallel graph capture failed and the runner fell back to eager
         self.steps_done = 0
 
-    def set_sampling(self, temperature=None, top_k=None, top_p=None, seed=None):
-        """Change the sampling parameters (a number for all sequences or one value per sequence) and / or reseed the draws.
-        Written into the runner's device tensors in place: a captured step picks them up at its next replay."""
-        if not self.sampling:
-            raise RuntimeError("set_sampling needs a runner built with sampling=True")
-        for dst, val in ((self.s_temperature, temperature), (self.s_top_k, top_k), (self.s_top_p, top_p)):
-            if val is not None:
-                dst.copy_(torch.as_tensor(val, dtype=dst.dtype).to(self.device).expand(self.B))
-        if seed is not None:
-            self.sample_gen.manual_seed(int(seed))
-
-    def _uniforms(self, *shape):
-        return torch.rand(shape, dtype=torch.float32, device=self.device, generator=self.sample_gen)
-
-    def _next_tokens(self, logits):
-        """self.tokens <- one token per sequence from logits fp16 [B, vocab] outside the captured step (prefill / extend):
-        arg-max, or a fresh draw on a sampling runner."""
-        if self.sampling:
-            self.s_u.copy_(self._uniforms(self.B))
-            fused_ext.sample(self.tokens, logits, self.s_temperature, self.s_top_k, self.s_top_p, self.s_u)
-        else:
-            self.tokens.copy_(torch.argmax(logits, dim=-1))
-
     def step(self):
         """Decode one token for every sequence (one HIP-graph replay once captured)."""
-        if self.sampling:
-            self.s_u.copy_(self._uniforms(self.B))      # outside the graph: the replay reads the buffer
+        self._refill_u()      # outside the graph: the replay reads the buffer
         if not self.use_graph:
             self._eager_step()
             self.steps_done += 1
@@ -689,6 +704,89 @@ class DecodeRunner:
             self.tokens.copy_(torch.argmax(logits, dim=-1))
 
     # ---- prefill (context stage) ---------------------------------------------------------------------------
+    def _context_bufs(self, T):
+        """T rows of each of the context stage's activation buffers (self._prefill_bufs).  Grow-only: the first call sizes them
+        to its own T (a chunked prefill's first chunk: the later ones are no longer), a call with more rows allocates anew,
+        one with fewer gets the head of what is there."""
+        c, dev, f16, i8 = self.cfg, self.device, torch.float16, torch.int8
+        buf = self._prefill_bufs
+        if buf is None or buf["T"] < T:
+            width = dict(x=(c.hidden, f16), qh=(c.hidden, i8), qi=(self.il, i8), qa=(self.hl * c.head_dim, i8),
+                         qkv=((self.hl + 2 * self.kl) * c.head_dim, f16), proj=(c.hidden, f16), gu=(2 * self.il, f16))
+            buf = dict(T=T)
+            buf.update((name, torch.empty((T, w), dtype=dt, device=dev)) for name, (w, dt) in width.items())
+            buf.update((name, torch.empty((T,), dtype=f16, device=dev)) for name in ("s1", "m1", "s2", "m2"))
+            self._prefill_bufs = buf
+        return [buf[name][:T] for name in ("x", "qh", "qi", "qa", "qkv", "proj", "gu", "s1", "m1", "s2", "m2")]
+
+    def _context_layers(self, n, tokens, write, attention):
+        """The ONE copy of the context stage's decoder layers (the sequence prefill() documents) on B * n rows, n per sequence, sequence
+        after sequence.  Its callers differ in two calls: write(qkv, lens, pad, table) -- RoPE on q / k in place + the rows' KV4 page
+        write (lens int32 [B] = n, pad: the padding offsets, table: the layer's block table) -- and attention(q, k, v, cu, table)
+        -> fp16 [B * n, heads, head_dim] (q / k / v: views of qkv, cu int32 [B + 1]).  Returns the rows' final hidden states [B * n,
+        hidden], a view of a buffer the next call reuses.  self.lengths is left alone."""
+        c, B, dev = self.cfg, self.B, self.device
+        T = B * n
+        hq, hk, d = self.hl, self.kl, c.head_dim
+        x, qh, qi, qa, qkv, proj, gu, sB, mB, sA, mA = self._context_bufs(T)
+        torch.index_select(self.embed, 0, tokens.reshape(-1), out=x)
+        lens = torch.full((B,), n, dtype=torch.int32, device=dev)
+        cu = torch.arange(0, B + 1, dtype=torch.int32, device=dev) * n
+        pad = fused_attention_fine_grained_dense.compute_padding_offsets(cu, n, T)
+        q = qkv[:, : hq * d].view(T, hq, d)
+        k = qkv[:, hq * d:(hq + hk) * d].view(T, hk, d)
+        v = qkv[:, (hq + hk) * d:].view(T, hk, d)
+        per_chn = c.group_size == -1
+        if not per_chn:
+            mA = mB = None      # g128: no activation sums (see _eager_step_body)
+        for li, Ly in enumerate(self.layers):
+            if li == 0 and per_chn:
+                layernorm_ops.rms_norm_general_fuse_sum(qh, x, Ly["ln1"], mB, sB, c.eps, True)
+            elif li == 0:
+                layernorm_ops.rms_norm_general(qh, x, Ly["ln1"], sB, c.eps, True)
+            else:
+                fused_ext.add_rms_norm_general_fuse_sum(qh, x, proj, Ly["ln1"], mB, sB, c.eps)
+            Ly["qkv"].forward(qh, sB, mB, qkv)
+            write(qkv, lens, pad, self.block_tables[li])
+            attn = attention(q, k, v, cu, self.block_tables[li])
+            if per_chn:
+                fused_kernels.invoke_quant_fuse_sum(qa, attn.view(T, hq * d), mA, sA)
+            else:
+                fused_kernels.invoke_quant(qa, attn.view(T, hq * d), sA)
+            Ly["o"].forward(qa, sA, mA, proj)
+            self._all_reduce(proj)
+            fused_ext.add_rms_norm_general_fuse_sum(qh, x, proj, Ly["ln2"], mB, sB, c.eps)
+            Ly["gate_up"].forward(qh, sB, mB, gu)
+            fused_ext.silu_mul_quant_fuse_sum(qi, gu, mA, sA)
+            Ly["down"].forward(qi, sA, mA, proj)
+            self._all_reduce(proj)
+        x.add_(proj)
+        return x
+
+    def _token_ids(self, tokens, count, expects):
+        """The caller's `count` token ids, or as many random ones.  expects: the error's head, e.g. "extend expects %d tokens"."""
+        if tokens is None:
+            return torch.randint(0, self.cfg.vocab, (count,), device=self.device, generator=self.gen)
+        if tokens.numel() != count:
+            raise ValueError("%s, got %d" % (expects % count, tokens.numel()))
+        return tokens
+
+    def _prompt(self, prompt_len, tokens):
+        """prefill()'s arguments checked: -> (the prompt length, the B * length token ids)."""
+        L = int(prompt_len if prompt_len is not None else self.lengths[0].item())
+        if L < 1 or L + 1 > self.max_context:
+            raise ValueError("prompt length does not fit the runner's KV pools")
+        return L, self._token_ids(tokens, self.B * L, "prefill expects %d prompt tokens")
+
+    def _next_from_last(self, x, n):
+        """The context stage's tail: the last of each sequence's n rows of x -> self.x, final norm -> self.normed, lm_head, and the
+        next token (arg-max, or a fresh draw on a sampling runner) -> self.tokens."""
+        c = self.cfg
+        self.x.copy_(x.view(self.B, n, c.hidden)[:, n - 1])
+        layernorm_ops.rms_norm(self.normed, self.x, self.final_norm, c.eps, False)
+        self._refill_u()
+        self._pick(torch.matmul(self.normed, self.lm_head.t()), fused_argmax=False)
+
     def prefill(self, prompt_len=None, tokens=None, chunk=None):
         """One context-stage pass over `prompt_len` tokens per sequence in the order of the reference's decoder
         layer at prefill shape (llama_w4a8_unpad.py:406-438 with M = B * prompt_len; ctx_update_kv.py:96-135;
@@ -703,87 +801,29 @@ class DecodeRunner:
         whole-prompt pass; chunk >= prompt_len is the whole-prompt pass."""
         if chunk is not None:
             return self._prefill_chunked(prompt_len, tokens, int(chunk))
-        import omniserve_backend.fused_attention_fine_grained_dense as fgd
         from .backend.prefill_attn import flash_attn_varlen_func
-        c, B, dev = self.cfg, self.B, self.device
-        L = int(prompt_len if prompt_len is not None else self.lengths[0].item())
-        if L < 1 or L + 1 > self.max_context:
-            raise ValueError("prompt length does not fit the runner's KV pools")
-        T = B * L
+        c, dev = self.cfg, self.device
         hq, hk, d = self.hl, self.kl, c.head_dim
-        f16, i8 = torch.float16, torch.int8
-        buf = getattr(self, "_prefill_bufs", None)
-        if buf is None or buf["T"] != T:
-            buf = dict(T=T, x=torch.empty((T, c.hidden), dtype=f16, device=dev),
-                       qh=torch.empty((T, c.hidden), dtype=i8, device=dev),
-                       qi=torch.empty((T, self.il), dtype=i8, device=dev),
-                       qa=torch.empty((T, hq * d), dtype=i8, device=dev),
-                       qkv=torch.empty((T, (hq + 2 * hk) * d), dtype=f16, device=dev),
-                       proj=torch.empty((T, c.hidden), dtype=f16, device=dev),
-                       gu=torch.empty((T, 2 * self.il), dtype=f16, device=dev),
-                       s1=torch.empty((T,), dtype=f16, device=dev), m1=torch.empty((T,), dtype=f16, device=dev),
-                       s2=torch.empty((T,), dtype=f16, device=dev), m2=torch.empty((T,), dtype=f16, device=dev))
-            self._prefill_bufs = buf
-        x, qh, qi, qa, qkv, proj, gu = buf["x"], buf["qh"], buf["qi"], buf["qa"], buf["qkv"], buf["proj"], buf["gu"]
-        sB, mB, sA, mA = buf["s1"], buf["m1"], buf["s2"], buf["m2"]
-        if tokens is None:
-            tokens = torch.randint(0, c.vocab, (T,), device=dev, generator=self.gen)
-        elif tokens.numel() != T:
-            raise ValueError("prefill expects %d prompt tokens, got %d" % (T, tokens.numel()))
-        torch.index_select(self.embed, 0, tokens, out=x)
-        lens = torch.full((B,), L, dtype=torch.int32, device=dev)
-        cu = torch.arange(0, B + 1, dtype=torch.int32, device=dev) * L
-        pad = fgd.compute_padding_offsets(cu, L, T)
+        L, tokens = self._prompt(prompt_len, tokens)
         flags = torch.ones((hk,), dtype=torch.int32, device=dev)
         rank = torch.arange(hk, dtype=torch.int32, device=dev)
-        q = qkv[:, : hq * d].view(T, hq, d)
-        k = qkv[:, hq * d:(hq + hk) * d].view(T, hk, d)
-        v = qkv[:, (hq + hk) * d:].view(T, hk, d)
-        per_chn = c.group_size == -1
-        if not per_chn:
-            mA = mB = None      # g128: no activation sums (see _eager_step_body)
-        for li, Ly in enumerate(self.layers):
-            if li == 0 and per_chn:
-                layernorm_ops.rms_norm_general_fuse_sum(qh, x, Ly["ln1"], mB, sB, c.eps, True)
-            elif li == 0:
-                layernorm_ops.rms_norm_general(qh, x, Ly["ln1"], sB, c.eps, True)
-            else:
-                fused_ext.add_rms_norm_general_fuse_sum(qh, x, proj, Ly["ln1"], mB, sB, c.eps)
-            Ly["qkv"].forward(qh, sB, mB, qkv)
-            fgd.apply_bias_rope_update_kv_cache(qkv, lens, None, pad, self.block_tables[li], None, flags, rank, hq, hk, L,
-                                                self.tpb, hk * d // 2, 0, 0, 0, 0, 0, hk, 0, d, c.rope_theta, 1.0,
-                                                1 << 20, True, True, True)
-            attn = flash_attn_varlen_func(q, k, v, cu, cu, L, L, causal=True)
-            if per_chn:
-                fused_kernels.invoke_quant_fuse_sum(qa, attn.view(T, hq * d), mA, sA)
-            else:
-                fused_kernels.invoke_quant(qa, attn.view(T, hq * d), sA)
-            Ly["o"].forward(qa, sA, mA, proj)
-            self._all_reduce(proj)
-            fused_ext.add_rms_norm_general_fuse_sum(qh, x, proj, Ly["ln2"], mB, sB, c.eps)
-            Ly["gate_up"].forward(qh, sB, mB, gu)
-            fused_ext.silu_mul_quant_fuse_sum(qi, gu, mA, sA)
-            Ly["down"].forward(qi, sA, mA, proj)
-            self._all_reduce(proj)
-        x.add_(proj)
-        last = x.view(B, L, c.hidden)[:, L - 1]
-        self.x.copy_(last)
-        layernorm_ops.rms_norm(self.normed, self.x, self.final_norm, c.eps, False)
-        self._next_tokens(torch.matmul(self.normed, self.lm_head.t()))
+
+        def write(qkv, lens, pad, table):      # the reference's writer with every head dense (ctx_update_kv.py:96-135)
+            fused_attention_fine_grained_dense.apply_bias_rope_update_kv_cache(
+                qkv, lens, None, pad, table, None, flags, rank, hq, hk, L, self.tpb, hk * d // 2, 0, 0, 0, 0, 0, hk, 0, d,
+                c.rope_theta, 1.0, 1 << 20, True, True, True)
+
+        def attention(q, k, v, cu, table):
+            return flash_attn_varlen_func(q, k, v, cu, cu, L, L, causal=True)
+
+        self._next_from_last(self._context_layers(L, tokens, write, attention), L)
         self.lengths.fill_(L)
 
     def _prefill_chunked(self, prompt_len, tokens, chunk):
-        c, B = self.cfg, self.B
-        L = int(prompt_len if prompt_len is not None else self.lengths[0].item())
         if chunk < 1:
             raise ValueError("chunk must be at least one token")
-        if L < 1 or L + 1 > self.max_context:
-            raise ValueError("prompt length does not fit the runner's KV pools")
-        if tokens is None:
-            tokens = torch.randint(0, c.vocab, (B * L,), device=self.device, generator=self.gen)
-        elif tokens.numel() != B * L:
-            raise ValueError("prefill expects %d prompt tokens, got %d" % (B * L, tokens.numel()))
-        tokens = tokens.view(B, L)
+        L, tokens = self._prompt(prompt_len, tokens)
+        tokens = tokens.view(self.B, L)
         self.lengths.zero_()
         for s in range(0, L, chunk):
             self.extend(min(chunk, L - s), tokens[:, s:s + chunk].reshape(-1))
@@ -795,7 +835,6 @@ class DecodeRunner:
         (fused_ext.prefill_attention_paged_kv4: quantised past, fresh chunk) in place of its writer / attention pair.  Updates
         self.lengths and leaves the next token in self.tokens.  `tokens`: B * new_len ids, sequence after sequence (default:
         random ids).  With nothing in the pools yet (every length 0) this is prefill(new_len, tokens) itself."""
-        c, B = self.cfg, self.B
         n = int(new_len)
         past_max = int(self.lengths.max().item())
         if n < 1:
@@ -804,14 +843,8 @@ class DecodeRunner:
             raise ValueError("lengths + new_len does not fit the runner's KV pools")
         if past_max == 0:
             return self.prefill(n, tokens)
-        if tokens is None:
-            tokens = torch.randint(0, c.vocab, (B * n,), device=self.device, generator=self.gen)
-        elif tokens.numel() != B * n:
-            raise ValueError("extend expects %d tokens, got %d" % (B * n, tokens.numel()))
-        x = self._extend_rows(n, tokens, past_max, fused_ext.prefill_attention_paged_kv4)
-        self.x.copy_(x.view(B, n, c.hidden)[:, n - 1])
-        layernorm_ops.rms_norm(self.normed, self.x, self.final_norm, c.eps, False)
-        self._next_tokens(torch.matmul(self.normed, self.lm_head.t()))
+        tokens = self._token_ids(tokens, self.B * n, "extend expects %d tokens")
+        self._next_from_last(self._extend_rows(n, tokens, past_max, fused_ext.prefill_attention_paged_kv4), n)
         self.lengths.add_(n)
 
     def _extend_rows(self, n, tokens, past_max, attention, rope_offsets=None):
@@ -821,64 +854,47 @@ class DecodeRunner:
         rope_offsets (verify_tree(): int32 [B * n], the nodes' depths): the rows still go to the slots lengths + i but are rotated
         at lengths + rope_offsets (fused_ext.kv4_prefill_write_at_pos); None: the plain writer at an offset.
         self.lengths is left alone."""
-        from .backend.fused_attention_fine_grained_dense import compute_padding_offsets
-        c, B, dev = self.cfg, self.B, self.device
-        T = B * n
-        hq, hk, d = self.hl, self.kl, c.head_dim
-        f16, i8 = torch.float16, torch.int8
-        buf = getattr(self, "_prefill_bufs", None)
-        if buf is None or buf["T"] < T:      # (a chunked prefill's first chunk sized them: the later ones are no longer)
-            buf = dict(T=T, x=torch.empty((T, c.hidden), dtype=f16, device=dev),
-                       qh=torch.empty((T, c.hidden), dtype=i8, device=dev),
-                       qi=torch.empty((T, self.il), dtype=i8, device=dev),
-                       qa=torch.empty((T, hq * d), dtype=i8, device=dev),
-                       qkv=torch.empty((T, (hq + 2 * hk) * d), dtype=f16, device=dev),
-                       proj=torch.empty((T, c.hidden), dtype=f16, device=dev),
-                       gu=torch.empty((T, 2 * self.il), dtype=f16, device=dev),
-                       s1=torch.empty((T,), dtype=f16, device=dev), m1=torch.empty((T,), dtype=f16, device=dev),
-                       s2=torch.empty((T,), dtype=f16, device=dev), m2=torch.empty((T,), dtype=f16, device=dev))
-            self._prefill_bufs = buf
-        x, qh, qi, qa, qkv, proj, gu = (buf[name][:T] for name in ("x", "qh", "qi", "qa", "qkv", "proj", "gu"))
-        sB, mB, sA, mA = (buf[name][:T] for name in ("s1", "m1", "s2", "m2"))
-        torch.index_select(self.embed, 0, tokens.reshape(-1), out=x)
-        lens = torch.full((B,), n, dtype=torch.int32, device=dev)
+        c, hq, hk = self.cfg, self.hl, self.kl
         past = self.lengths.clone()
-        cu = torch.arange(0, B + 1, dtype=torch.int32, device=dev) * n
-        pad = compute_padding_offsets(cu, n, T)
-        q = qkv[:, : hq * d].view(T, hq, d)
-        k = qkv[:, hq * d:(hq + hk) * d].view(T, hk, d)
-        v = qkv[:, (hq + hk) * d:].view(T, hk, d)
-        per_chn = c.group_size == -1
-        if not per_chn:
-            mA = mB = None      # g128: no activation sums (see _eager_step_body)
-        for li, Ly in enumerate(self.layers):
-            if li == 0 and per_chn:
-                layernorm_ops.rms_norm_general_fuse_sum(qh, x, Ly["ln1"], mB, sB, c.eps, True)
-            elif li == 0:
-                layernorm_ops.rms_norm_general(qh, x, Ly["ln1"], sB, c.eps, True)
-            else:
-                fused_ext.add_rms_norm_general_fuse_sum(qh, x, proj, Ly["ln1"], mB, sB, c.eps)
-            Ly["qkv"].forward(qh, sB, mB, qkv)
+
+        def write(qkv, lens, pad, table):
             if rope_offsets is None:
-                fused_ext.kv4_prefill_write_at(qkv, lens, past, pad, self.block_tables[li], hq, hk, n, self.tpb, past_max + n,
-                                               c.rope_theta, 1.0, 1 << 20)
+                fused_ext.kv4_prefill_write_at(qkv, lens, past, pad, table, hq, hk, n, self.tpb, past_max + n, c.rope_theta, 1.0,
+                                               1 << 20)
             else:
-                fused_ext.kv4_prefill_write_at_pos(qkv, lens, past, rope_offsets, pad, self.block_tables[li], hq, hk, n,
-                                                   self.tpb, past_max + n, c.rope_theta, 1.0, 1 << 20)
-            attn = attention(q, k, v, cu, past, self.block_tables[li], self.tpb, n)
-            if per_chn:
-                fused_kernels.invoke_quant_fuse_sum(qa, attn.view(T, hq * d), mA, sA)
-            else:
-                fused_kernels.invoke_quant(qa, attn.view(T, hq * d), sA)
-            Ly["o"].forward(qa, sA, mA, proj)
-            self._all_reduce(proj)
-            fused_ext.add_rms_norm_general_fuse_sum(qh, x, proj, Ly["ln2"], mB, sB, c.eps)
-            Ly["gate_up"].forward(qh, sB, mB, gu)
-            fused_ext.silu_mul_quant_fuse_sum(qi, gu, mA, sA)
-            Ly["down"].forward(qi, sA, mA, proj)
-            self._all_reduce(proj)
-        x.add_(proj)
-        return x
+                fused_ext.kv4_prefill_write_at_pos(qkv, lens, past, rope_offsets, pad, table, hq, hk, n, self.tpb, past_max + n,
+                                                   c.rope_theta, 1.0, 1 << 20)
+
+        return self._context_layers(n, tokens, write, lambda q, k, v, cu, table: attention(q, k, v, cu, past, table, self.tpb, n))
+
+    def _pending_rows(self, what, rows, limit, expects, unit, size):
+        """The entry checks of verify() / verify_tree() on their int64 [B, n] token rows, whose column 0 must be the pending
+        tokens and which must fit the pools behind the longest sequence.  what: the calling method; expects / unit / size: its
+        words for the rows (the last word of expects names them), one of them and their count.  -> (rows on the device, n,
+        the longest sequence's length)."""
+        if rows.dim() != 2 or rows.shape[0] != self.B or rows.dtype != torch.int64:
+            raise ValueError("%s expects %s" % (what, expects))
+        n = int(rows.shape[1])
+        if n < 1 or n > limit:
+            raise ValueError("%s takes 1 to %d %s per sequence, got %d" % (what, limit, unit, n))
+        rows = rows.to(self.device)
+        if not bool((rows[:, 0] == self.tokens).all().item()):
+            raise ValueError("%s: column 0 of the %s must be the runner's pending tokens" % (what, expects.split()[-1]))
+        past_max = int(self.lengths.max().item())
+        if past_max + n + 1 > self.max_context:
+            raise ValueError("lengths + %s does not fit the runner's KV pools" % size)
+        return rows, n, past_max
+
+    def _keep(self, x, normed, pred, last, counts):
+        """The tail of verify() / verify_tree(): position last[b] (int64 [B, 1]) of sequence b's n scored ones is the one kept --
+        its hidden state -> self.x, its normed state -> self.normed, the model's token behind it -> self.tokens -- and the
+        sequence grows by counts[b] (int32 [B])."""
+        B, n = pred.shape
+        pick = last.view(B, 1, 1).expand(B, 1, self.cfg.hidden)
+        self.x.copy_(x.view(B, n, -1).gather(1, pick).squeeze(1))
+        self.normed.copy_(normed.view(B, n, -1).gather(1, pick).squeeze(1))
+        self.tokens.copy_(pred.gather(1, last).squeeze(1))
+        self.lengths.add_(counts)
 
     def verify(self, draft, sampled=None, uniforms=None):
         """One multi-token decode step (the verify step of speculative decoding): score n = draft.shape[1] <= 8 positions per
@@ -899,17 +915,8 @@ class DecodeRunner:
         sampled = self.sampling if sampled is None else bool(sampled)
         if sampled and not self.sampling:
             raise RuntimeError("verify(sampled=True) needs a runner built with sampling=True")
-        if draft.dim() != 2 or draft.shape[0] != B or draft.dtype != torch.int64:
-            raise ValueError("verify expects an int64 [B, n] draft")
-        n = int(draft.shape[1])
-        if n < 1 or n > fused_ext.DECODE_MULTI_MAX_Q:
-            raise ValueError("verify takes 1 to %d positions per sequence, got %d" % (fused_ext.DECODE_MULTI_MAX_Q, n))
-        draft = draft.to(self.device)
-        if not bool((draft[:, 0] == self.tokens).all().item()):
-            raise ValueError("verify: column 0 of the draft must be the runner's pending tokens")
-        past_max = int(self.lengths.max().item())
-        if past_max + n + 1 > self.max_context:
-            raise ValueError("lengths + draft length does not fit the runner's KV pools")
+        draft, n, past_max = self._pending_rows("verify", draft, fused_ext.DECODE_MULTI_MAX_Q, "an int64 [B, n] draft",
+                                                "positions", "draft length")
 
         def attention(q, k, v, cu, past, table, tpb, n_):
             return fused_ext.decode_attention_multi_kv4(q, k, v, cu, past, table, tpb, n_, past_max)
@@ -931,12 +938,7 @@ class DecodeRunner:
         else:
             pred = torch.argmax(logits, dim=-1).view(B, n)
             m = accept_lengths(draft, pred)
-        last = (m - 1).view(B, 1)
-        pick = last.view(B, 1, 1).expand(B, 1, c.hidden)
-        self.x.copy_(x.view(B, n, c.hidden).gather(1, pick).squeeze(1))
-        self.normed.copy_(normed.view(B, n, c.hidden).gather(1, pick).squeeze(1))
-        self.tokens.copy_(pred.gather(1, last).squeeze(1))
-        self.lengths.add_(m.to(torch.int32))
+        self._keep(x, normed, pred, (m - 1).view(B, 1), m.to(torch.int32))
         return pred, m
 
     def verify_tree(self, tokens, parents):
@@ -954,20 +956,11 @@ class DecodeRunner:
         if self.sampling:
             raise NotImplementedError("verify_tree on a sampling runner: multi-branch rejection sampling is not built; the tree "
                                       "step is greedy only (use verify() for sampled speculative decoding)")
-        if tokens.dim() != 2 or tokens.shape[0] != B or tokens.dtype != torch.int64:
-            raise ValueError("verify_tree expects int64 [B, n] tokens")
-        n = int(tokens.shape[1])
-        if n < 1 or n > fused_ext.DECODE_TREE_MAX_Q:
-            raise ValueError("verify_tree takes 1 to %d nodes per sequence, got %d" % (fused_ext.DECODE_TREE_MAX_Q, n))
+        tokens, n, past_max = self._pending_rows("verify_tree", tokens, fused_ext.DECODE_TREE_MAX_Q, "int64 [B, n] tokens",
+                                                 "nodes", "tree size")
         par = [int(p) for p in (parents.tolist() if torch.is_tensor(parents) else parents)]
         if len(par) != n or par[0] != -1 or any(not 0 <= par[i] < i for i in range(1, n)):
             raise ValueError("verify_tree: parents must hold n entries with parents[0] = -1 and 0 <= parents[i] < i")
-        tokens = tokens.to(self.device)
-        if not bool((tokens[:, 0] == self.tokens).all().item()):
-            raise ValueError("verify_tree: column 0 of the tokens must be the runner's pending tokens")
-        past_max = int(self.lengths.max().item())
-        if past_max + n + 1 > self.max_context:
-            raise ValueError("lengths + tree size does not fit the runner's KV pools")
         mask1, depth1 = fused_ext.tree_masks(torch.tensor(par, dtype=torch.int64))
         mask = mask1.repeat(B).to(self.device)
         depth = depth1.repeat(B).to(self.device)
@@ -983,12 +976,7 @@ class DecodeRunner:
         src, counts = path.to(torch.int32).contiguous(), m.to(torch.int32)
         for table in self.block_tables:
             fused_ext.kv4_compact_rows(table, self.lengths, src, counts, self.tpb, self.kl)
-        last = path.gather(1, (m - 1).view(B, 1))
-        pick = last.view(B, 1, 1).expand(B, 1, c.hidden)
-        self.x.copy_(x.view(B, n, c.hidden).gather(1, pick).squeeze(1))
-        self.normed.copy_(normed.view(B, n, c.hidden).gather(1, pick).squeeze(1))
-        self.tokens.copy_(pred.gather(1, last).squeeze(1))
-        self.lengths.add_(counts)
+        self._keep(x, normed, pred, path.gather(1, (m - 1).view(B, 1)), counts)
         return pred, path, m
 
     def _all_reduce(self, buf):

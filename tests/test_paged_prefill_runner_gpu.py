@@ -2,9 +2,10 @@
 import pytest
 import torch
 
+from runner_cases import B, L, pools as _pools, prompt as _prompt, rel_l2 as _rel_l2, runner as _runner
+
 pytestmark = pytest.mark.gpu
 
-B, L = 3, 150
 # Relative L2 distance of the final-norm hidden states between two summation orders of the EXISTING decode attention kernel
 # (path A below with omni_kv4_decode_set_split_override(1) and (4)), measured on the MI355X on the parent commit: the
 # noise floor of "the same mathematics through another kernel".  See test_one_token_through_decode_and_through_extend.
@@ -12,28 +13,8 @@ NOISE_FLOOR = 0.0517
 FACTOR = 4.0
 
 
-def _runner(seed=11):
-    from omniserve_amd.runtime import DecodeRunner, LlamaConfig
-    return DecodeRunner(LlamaConfig.tiny(), B, 70, 100, torch.device("cuda:0"), seed=seed, use_graph=False, fused=2)
-
-
-def _prompt(r, n=L):
-    g = torch.Generator(device=r.device)
-    g.manual_seed(5)
-    return torch.randint(0, r.cfg.vocab, (B, n), device=r.device, generator=g)
-
-
-def _pools(r):
-    return [[p.clone() for p in layer] for layer in r.pools]
-
-
 def _same_pools(a, b):
     return all(torch.equal(pa, pb) for la, lb in zip(a, b) for pa, pb in zip(la, lb))
-
-
-def _rel_l2(a, b):
-    a, b = a.double(), b.double()
-    return float(((a - b).norm(dim=-1) / b.norm(dim=-1)).max())
 
 
 def test_one_chunk_is_the_whole_prompt_pass_bit_for_bit():
@@ -150,3 +131,37 @@ def test_extend_beyond_the_pools_raises():
     assert r.lengths.tolist() == [L + room] * B
     with pytest.raises(ValueError):
         r.extend(1)
+
+
+def _first_rows(r, count):
+    """The bytes of positions [0, count) of every layer's K and V pages (count <= one page): codes, scales and zero points."""
+    hk, tpb = r.kl, r.tpb
+    data = hk * tpb * 64
+    out = []
+    for table, layer in zip(r.block_tables, r.pools):
+        for kv, pool in enumerate(layer):
+            pages = pool[(table[:, kv, 0] - pool.data_ptr()) // r.page_bytes]
+            out.append(pages[:, :data].view(B, hk, tpb, 64)[:, :, :count].clone())
+            out.append(pages[:, data:].view(B, 2, hk, tpb, 2)[:, :, :, :count].clone())
+    return out
+
+
+def test_prefill_into_larger_buffers_is_a_fresh_runners_prefill():
+    """The context stage's buffers only grow: prefill(40) behind prefill(150) runs in the head of the 150-token buffers.  x, normed,
+    tokens, lengths and the page bytes of positions [0, 40) equal a fresh runner's prefill(40), whose buffers hold exactly its own
+    rows, bit for bit."""
+    r = _runner()
+    r.prefill(L, _prompt(r).reshape(-1))
+    prompt40 = _prompt(r, 40)
+    r.prefill(40, prompt40.reshape(-1))
+    assert r._prefill_bufs["T"] == B * L
+    f = _runner()
+    f.prefill(40, prompt40.reshape(-1))
+    torch.cuda.synchronize()
+    assert f._prefill_bufs["T"] == B * 40
+    assert torch.equal(r.x.view(torch.int16), f.x.view(torch.int16))
+    assert torch.equal(r.normed.view(torch.int16), f.normed.view(torch.int16))
+    assert torch.equal(r.tokens, f.tokens)
+    assert r.lengths.tolist() == [40] * B and f.lengths.tolist() == [40] * B
+    for a, b in zip(_first_rows(r, 40), _first_rows(f, 40)):
+        assert torch.equal(a, b)

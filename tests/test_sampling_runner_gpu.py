@@ -4,33 +4,9 @@ import pytest
 import torch
 
 import sampling_cases as sc
+from runner_cases import B, L, N, prefilled as _prefilled, random_draft as _random_draft, restore as _restore
 
 pytestmark = pytest.mark.gpu
-
-B, L, N = 3, 150, 4
-
-
-def _runner(sampling, use_graph=False):
-    from omniserve_amd.runtime import DecodeRunner, LlamaConfig
-    return DecodeRunner(LlamaConfig.tiny(), B, 70, 100, torch.device("cuda:0"), seed=11, use_graph=use_graph, fused=2,
-                        sampling=sampling)
-
-
-def _prefilled(sampling, use_graph=False, **params):
-    r = _runner(sampling, use_graph)
-    if params:
-        r.set_sampling(**params)
-    g = torch.Generator(device=r.device)
-    g.manual_seed(5)
-    prompt = torch.randint(0, r.cfg.vocab, (B, L), device=r.device, generator=g)
-    r.prefill(L, prompt.reshape(-1))
-    return r, (r.lengths.clone(), r.tokens.clone())
-
-
-def _restore(r, state):
-    r.lengths.copy_(state[0])
-    r.tokens.copy_(state[1])
-
 
 def _steps(r, n, logits=None):
     toks = []
@@ -83,13 +59,6 @@ def test_sampled_steps_are_reproducible_graph_equals_eager_tokens_are_kept():
     _steps(d, 8)
     d.set_sampling(temperature=2.5, top_k=0, top_p=1.0, seed=3)
     assert not torch.equal(_steps(d, 8), t2a), "another seed drew the same 24 tokens at T = 2.5"
-
-
-def _random_draft(r, seed):
-    g = torch.Generator(device=r.device)
-    g.manual_seed(seed)
-    tail = torch.randint(0, r.cfg.vocab, (B, N - 1), device=r.device, generator=g)
-    return torch.cat([r.tokens.view(B, 1), tail], dim=1)
 
 
 def test_sampled_verify_at_temperature_zero_is_the_greedy_verify():

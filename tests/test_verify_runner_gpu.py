@@ -2,45 +2,16 @@
 import pytest
 import torch
 
+from runner_cases import (B, N, four_steps as _four_steps, prefilled as _prefilled, random_draft as _random_draft,
+                          rel_l2 as _rel_l2, restore as _restore)
+
 pytestmark = pytest.mark.gpu
 
-B, L, N = 3, 150, 4
 # The noise floor of "the same mathematics through another kernel" that tests/test_paged_prefill_runner_gpu.py pins (the parent's
 # decode kernel forced to 1 against 4 KV splits, final-norm hidden states, relative L2: DESIGN.md section 4.5a), and its factor:
 # two changed summation orders, S and P.V.
 NOISE_FLOOR = 0.0517
 FACTOR = 4.0
-
-
-def _runner(seed=11):
-    from omniserve_amd.runtime import DecodeRunner, LlamaConfig
-    return DecodeRunner(LlamaConfig.tiny(), B, 70, 100, torch.device("cuda:0"), seed=seed, use_graph=False, fused=2)
-
-
-def _prefilled():
-    r = _runner()
-    g = torch.Generator(device=r.device)
-    g.manual_seed(5)
-    prompt = torch.randint(0, r.cfg.vocab, (B, L), device=r.device, generator=g)
-    r.prefill(L, prompt.reshape(-1))
-    return r, (r.lengths.clone(), r.tokens.clone())
-
-
-def _restore(r, state):
-    r.lengths.copy_(state[0])
-    r.tokens.copy_(state[1])
-
-
-def _random_draft(r, seed):
-    g = torch.Generator(device=r.device)
-    g.manual_seed(seed)
-    tail = torch.randint(0, r.cfg.vocab, (B, N - 1), device=r.device, generator=g)
-    return torch.cat([r.tokens.view(B, 1), tail], dim=1)
-
-
-def _rel_l2(a, b):
-    a, b = a.double(), b.double()
-    return float(((a - b).norm(dim=-1) / b.norm(dim=-1)).max())
 
 
 def test_verify_converges_on_its_own_predictions_and_matches_extend():
@@ -90,15 +61,6 @@ def test_verify_column_zero_must_be_the_pending_token():
         r.verify(draft)
     with pytest.raises(ValueError):
         r.verify(torch.zeros((B, 9), dtype=torch.int64, device=r.device))
-
-
-def _four_steps(r):
-    toks = []
-    for _ in range(4):
-        r.step()
-        toks.append(r.tokens.clone())
-    torch.cuda.synchronize()
-    return torch.stack(toks), r.x.clone()
 
 
 def test_rollback_is_harmless():

@@ -3,48 +3,15 @@ step() from the same restored state."""
 import pytest
 import torch
 
+from runner_cases import (B, N, four_steps as _four_steps, pools as _pools, prefilled as _prefilled,
+                          random_draft as _random_draft, rel_l2 as _rel_l2, restore as _restore)
+
 pytestmark = pytest.mark.gpu
 
-B, L, N = 3, 150, 4
 # The bar of tests/test_verify_runner_gpu.py for "the same mathematics through another kernel / another summation order":
 # final-norm hidden states, relative L2 <= 4 x the noise floor that DESIGN.md section 4.5a pins.
 NOISE_FLOOR = 0.0517
 FACTOR = 4.0
-
-
-def _runner(seed=11):
-    from omniserve_amd.runtime import DecodeRunner, LlamaConfig
-    return DecodeRunner(LlamaConfig.tiny(), B, 70, 100, torch.device("cuda:0"), seed=seed, use_graph=False, fused=2)
-
-
-def _prefilled():
-    r = _runner()
-    g = torch.Generator(device=r.device)
-    g.manual_seed(5)
-    prompt = torch.randint(0, r.cfg.vocab, (B, L), device=r.device, generator=g)
-    r.prefill(L, prompt.reshape(-1))
-    return r, (r.lengths.clone(), r.tokens.clone())
-
-
-def _restore(r, state):
-    r.lengths.copy_(state[0])
-    r.tokens.copy_(state[1])
-
-
-def _random_draft(r, seed, n=N):
-    g = torch.Generator(device=r.device)
-    g.manual_seed(seed)
-    tail = torch.randint(0, r.cfg.vocab, (B, n - 1), device=r.device, generator=g)
-    return torch.cat([r.tokens.view(B, 1), tail], dim=1)
-
-
-def _rel_l2(a, b):
-    a, b = a.double(), b.double()
-    return float(((a - b).norm(dim=-1) / b.norm(dim=-1)).max())
-
-
-def _pools(r):
-    return [[p.clone() for p in layer] for layer in r.pools]
 
 
 def _layer0_rows(r, pools, past, count):
@@ -131,15 +98,6 @@ def test_a_true_path_among_decoys():
     print(msg)
     assert dist <= FACTOR * NOISE_FLOOR, msg
     assert torch.equal(r.tokens, chain[1]) or dist > 0       # (the next token may only differ where the hidden states do)
-
-
-def _four_steps(r):
-    toks = []
-    for _ in range(4):
-        r.step()
-        toks.append(r.tokens.clone())
-    torch.cuda.synchronize()
-    return torch.stack(toks), r.x.clone()
 
 
 def test_all_drafts_wrong():
