@@ -318,6 +318,21 @@ int omni_sample_f16(void* token_out_i64, void* probe_prob_out_f32, const void* l
                     int cols, const void* temperature_f32, const void* top_k_i32, const void* top_p_f32, const void* u_f32,
                     const void* probe_i64, const void* exclude_i64, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Log-probabilities (contract: DESIGN.md section 4.6a).  Stands in for what upstream computes nowhere: SamplingParams.logprobs /
+ * prompt_logprobs (omniserve/sampling_params.py:69-75) are accepted and carried through Sequence / SequenceOutput but its
+ * sampler never fills them.  logits fp16 [rows, cols] with a row stride (any alignment, cols <= 2^22, rows <= 65535), read as
+ * the RAW distribution: lse_out_f32[r] = max + ln sum exp(x - max) (nullable); with target_i64 [rows] on the device
+ * token_logprob_out_f32[r] = x[target] - lse and rank_out_i32[r] = the target's 1-based position in the canonical order (value
+ * descending by omni_argmax_f16's key, then index ascending) -- both nullable, NaN / 0 for a target outside [0, cols);
+ * top_token_out_i64 / top_logprob_out_f32 [rows, n_top] (0 <= n_top <= 20; ignored when n_top == 0): the first n_top tokens in
+ * that order and their log-probabilities, -1 / -inf behind the last column.  A row whose maximum is NaN / +inf or that holds
+ * nothing but -inf: every log-probability NaN, order and rank as the key says.  Deterministic; no host read, no allocation.
+ * workspace >= omni_logprob_workspace_bytes(rows, cols, n_top). */
+size_t omni_logprob_workspace_bytes(int rows, int cols, int n_top);
+int omni_logprob_f16(void* lse_out_f32, void* token_logprob_out_f32, void* rank_out_i32, void* top_token_out_i64,
+                     void* top_logprob_out_f32, const void* logits_f16, int64_t row_stride, int rows, int cols,
+                     const void* target_i64, int n_top, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Embedding lookup of the decode drivers (torch.nn.Embedding upstream): out fp16 [rows, cols] = table[idx[r], :],
  * idx int64 [rows] on the device; cols % 8 == 0; ids outside [0, table_rows) leave their row untouched. */
 int omni_gather_rows_f16(void* out_f16, const void* table_f16, const void* idx_i64, int rows, int cols,

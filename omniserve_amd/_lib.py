@@ -107,6 +107,8 @@ PROTOTYPES = {
     "omni_argmax_f16": (_i, [_vp, _vp, _i64, _i, _i, _vp, _sz, _vp]),
     "omni_sample_workspace_bytes": (_sz, [_i, _i]),
     "omni_sample_f16": (_i, [_vp, _vp, _vp, _i64, _i, _i] + [_vp] * 6 + [_vp, _sz, _vp]),
+    "omni_logprob_workspace_bytes": (_sz, [_i, _i, _i]),
+    "omni_logprob_f16": (_i, [_vp] * 6 + [_i64, _i, _i, _vp, _i, _vp, _sz, _vp]),
     "omni_kv4_prefill_write_fine_grained": (_i, [_vp] * 7 + [_i] * 15 + [_vp, _i, _i, _vp]),
     "omni_kv4_decode_attention_fine_grained": (_i, [_vp, _vp, _vp, _vp, _i64, _i64] + [_vp] * 6 + [_i] * 16 + [_vp, _i, _vp, _sz, _vp]),
     "omni_kv8_prefill_write_per_tensor": (_i, [_vp] * 8 + [_i] * 15 + [_vp, _i, _i, _vp]),

@@ -1,5 +1,7 @@
 """Opt-in fused entry points (NOT in the reference's omniserve_backend).
 Each is bit-identical to the pair of reference calls it replaces."""
+import collections
+
 import torch
 
 from .. import _lib
@@ -490,6 +492,64 @@ def sample(out, logits, temperature, top_k, top_p, u, probe=None, exclude=None, 
                                     temperature.data_ptr(), top_k.data_ptr(), top_p.data_ptr(), u.data_ptr(), _ptr(probe),
                                     _ptr(exclude), ws.data_ptr(), ws.numel(), _lib.current_stream())
     _lib.check(rc, "fused_ext.sample")
+
+
+LOGPROB_MAX_TOP = 20     # csrc/logprob.hip
+LOGPROB_CHUNKS = 32      # workgroups per row; a chunk is logprob_chunk_cols(cols) columns
+LOGPROB_VEC = 8          # columns per 16-byte load (row stride % 8 == 0 and a 16-byte aligned base)
+
+LogProbs = collections.namedtuple("LogProbs", "lse token_logprob rank top_tokens top_logprobs")
+
+
+def logprob_chunk_cols(cols):
+    """Columns per chunk of the log-probability kernels: a function of cols only (part of the determinism contract)."""
+    return ((cols + LOGPROB_CHUNKS - 1) // LOGPROB_CHUNKS + LOGPROB_VEC - 1) // LOGPROB_VEC * LOGPROB_VEC
+
+
+def logprobs(logits, target=None, n_top=0, lse=None, token_logprob=None, rank=None, top_tokens=None, top_logprobs=None):
+    """Log-probabilities under the RAW distribution of each row of logits fp16 [rows, cols] (no temperature, no filter): what the
+    reference's SamplingParams.logprobs / prompt_logprobs ask for and its sampler never fills.  lse f32 [rows] = max + ln sum
+    exp(x - max); with target int64 [rows]: token_logprob f32 [rows] = x[target] - lse and rank int32 [rows] = the target's
+    1-based position in the canonical order (value descending by fused_ext.argmax's key, then index ascending); NaN / 0 for a
+    target outside [0, cols); with n_top in 1 .. LOGPROB_MAX_TOP: top_tokens int64 / top_logprobs f32 [rows, n_top], the first
+    n_top tokens in that order (-1 / -inf behind the last column).  Outputs that are not passed are allocated (token_logprob /
+    rank only with a target, the top lists only with n_top > 0).  -> LogProbs(lse, token_logprob, rank, top_tokens,
+    top_logprobs), None where nothing was computed.  Contract: DESIGN.md section 4.6a."""
+    if logits.dtype != torch.float16 or logits.dim() != 2 or logits.stride(1) != 1:
+        raise RuntimeError("logprobs: logits must be fp16 [rows, cols] with contiguous rows")
+    rows, cols = logits.shape
+    dev = logits.device
+    n_top = int(n_top)
+    if not 0 <= n_top <= LOGPROB_MAX_TOP:
+        raise ValueError("logprobs: n_top must be in 0 .. %d, got %d" % (LOGPROB_MAX_TOP, n_top))
+    if target is None and (token_logprob is not None or rank is not None):
+        raise RuntimeError("logprobs: token_logprob / rank need target")
+    if n_top == 0 and (top_tokens is not None or top_logprobs is not None):
+        raise RuntimeError("logprobs: top_tokens / top_logprobs need n_top > 0")
+    if target is not None and (target.dtype != torch.int64 or target.numel() != rows or not target.is_contiguous()):
+        raise RuntimeError("logprobs: target must be a contiguous int64 tensor with one entry per row")
+
+    def out(t, name, shape, dtype, wanted):
+        if t is None:
+            return torch.empty(shape, dtype=dtype, device=dev) if wanted else None
+        if t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous():
+            raise RuntimeError("logprobs: %s must be a contiguous %s %s tensor" %
+                               (name, str(dtype).replace("torch.", ""), list(shape)))
+        return t
+
+    lse = out(lse, "lse", (rows,), torch.float32, True)
+    token_logprob = out(token_logprob, "token_logprob", (rows,), torch.float32, target is not None)
+    rank = out(rank, "rank", (rows,), torch.int32, target is not None)
+    top_tokens = out(top_tokens, "top_tokens", (rows, n_top), torch.int64, n_top > 0)
+    top_logprobs = out(top_logprobs, "top_logprobs", (rows, n_top), torch.float32, n_top > 0)
+    _lib.require_cuda(logits, target, lse, token_logprob, rank, top_tokens, top_logprobs)
+    need = _lib.lib().omni_logprob_workspace_bytes(rows, cols, n_top)
+    ws = _lib.workspace(need, dev, "logprob")
+    rc = _lib.lib().omni_logprob_f16(_ptr(lse), _ptr(token_logprob), _ptr(rank), _ptr(top_tokens), _ptr(top_logprobs),
+                                     logits.data_ptr(), logits.stride(0), rows, cols, _ptr(target), n_top, ws.data_ptr(),
+                                     ws.numel(), _lib.current_stream())
+    _lib.check(rc, "fused_ext.logprobs")
+    return LogProbs(lse, token_logprob, rank, top_tokens, top_logprobs)
 
 
 def select_topk_pages(out, scores, subs_per_page, total_pages, k):

@@ -15,6 +15,7 @@ eagerly; at MI355X speeds the step is launch-bound otherwise).
 """
 from __future__ import annotations
 
+import collections
 import dataclasses
 
 import torch
@@ -174,6 +175,20 @@ def accept_paths(parents, tokens, pred):
     return path, m
 
 
+ScoreResult = collections.namedtuple("ScoreResult", "logprob rank top_tokens top_logprobs")
+
+
+def perplexity(logprob, mask=None):
+    """exp(-mean log-probability) per sequence: logprob [B, n] (DecodeRunner.score's), mask bool [B, n] (None: every position
+    counts) -> f64 [B].  A -inf log-probability gives inf.  Pure tensor arithmetic (CPU or device)."""
+    lp = logprob.to(torch.float64)
+    if mask is None:
+        return torch.exp(-lp.mean(dim=1))
+    keep = mask.to(torch.bool)
+    total = torch.where(keep, lp, torch.zeros_like(lp)).sum(dim=1)
+    return torch.exp(-total / keep.sum(dim=1).to(torch.float64))
+
+
 class SamplingState:
     """Sampled decoding's state and its two operations, for DecodeRunner and lserve_runtime.LServeDecodeRunner (a mixin: the
     runners keep the attributes).  The per-row parameters and the draw u live in device tensors that a captured step READS, so
@@ -228,7 +243,7 @@ class DecodeRunner(SamplingState):
                  use_graph=True, fused=True, tp_rank=0, tp_size=1, tp_group=None, shard_full=False,
                  prefetch_mb=None, prefetch_blocks=160, weight_policy=1, tp_comm=None, max_fused=4, tp_l2_attn=True,
                  l3_prefetch_down=1, qkv_slabs="auto", attn_single=True, arm_qkv=True, arm_o=True, l3_last=True,
-                 sampling=False):
+                 sampling=False, logprobs=None):
         """tp_size > 1: Megatron-style tensor parallelism (omniserve_amd/tp.py): qkv / gate_up column-parallel,
         o / down row-parallel, attention by kv head, one fp16 sum all-reduce of the [B, hidden] projection after
         o_proj and after down_proj.  shard_full=True builds the full layers from the seed and keeps this
@@ -238,7 +253,15 @@ class DecodeRunner(SamplingState):
         fusion level the runner may pick; tp_l2_attn / qkv_slabs ("auto", True, False) / attn_single / arm_qkv / arm_o /
         l3_prefetch_down (0, 1, 2) / l3_last select the forms described where they are used below.
         sampling=True: every token is drawn by fused_ext.sample (temperature / top-p / top-k) instead of
-        arg-max; the parameters start at temperature 0, i.e. greedy, and set_sampling() changes them."""
+        arg-max; the parameters start at temperature 0, i.e. greedy, and set_sampling() changes them.
+        logprobs (None: off; 0: the pending token's log-probability and rank; N in 1 .. 20: the top N as well): after every method
+        that sets self.tokens the buffers token_logprob f32 [B], token_rank i32 [B], top_tokens i64 [B, N] and top_logprobs f32
+        [B, N] describe that token under the RAW distribution of the logits row it was picked from (fused_ext.logprobs, DESIGN.md
+        section 4.6a) -- greedy or sampled alike.  Read-only: tokens and state are the same bits with or without it."""
+        if logprobs is not None and (isinstance(logprobs, bool) or not isinstance(logprobs, int) or
+                                     not 0 <= logprobs <= fused_ext.LOGPROB_MAX_TOP):
+            raise ValueError("logprobs must be None or an integer in 0 .. %d, got %r" % (fused_ext.LOGPROB_MAX_TOP, logprobs))
+        self.logprobs = logprobs
         self.cfg, self.B, self.device = cfg, batch, device
         self.tp_rank, self.tp_size, self.tp_group = int(tp_rank), int(tp_size), tp_group
         # tp_comm = "peer": the decode step's collectives run on the library's own peer-mapped all-reduce (tp.PeerComm: one
@@ -431,6 +454,16 @@ class DecodeRunner(SamplingState):
         self._init_sampling(sampling, B, device, seed)
         if self.sampling:
             _lib.workspace(_lib.lib().omni_sample_workspace_bytes(8 * B, c.vocab), device, "sample")    # (verify: B * 8 rows)
+        if self.logprobs is not None:
+            self.token_logprob = torch.zeros((B,), dtype=torch.float32, device=device)
+            self.token_rank = torch.zeros((B,), dtype=torch.int32, device=device)
+            self.top_tokens = torch.full((B, self.logprobs), -1, dtype=torch.int64, device=device)
+            self.top_logprobs = torch.zeros((B, self.logprobs), dtype=torch.float32, device=device)
+            self._lse = torch.zeros((B,), dtype=torch.float32, device=device)
+            # (verify_tree: B * 32 rows; sized now so that no later eager call moves the buffer a captured step points to)
+            _lib.workspace(_lib.lib().omni_logprob_workspace_bytes(fused_ext.DECODE_TREE_MAX_Q * B, c.vocab, self.logprobs),
+                           device, "logprob")
+        self._score_rows = None       # score()'s tap on the context stage's rows (_next_from_last)
         self._prefill_bufs = None     # the context stage's activation buffers (_context_bufs)
         rope_table(self.max_context + 1, c.head_dim, c.rope_theta, 1.0, device)  # pre-build (capture safe)
         self.graph = None
@@ -702,6 +735,24 @@ class DecodeRunner(SamplingState):
             fused_ext.argmax(self.tokens, logits)      # same result as torch.argmax, 6 us instead of 47
         else:
             self.tokens.copy_(torch.argmax(logits, dim=-1))
+        self._record_logprobs(logits)
+
+    # ---- log-probabilities ------------------------------------------------------------
+    def _record_logprobs(self, logits):
+        """The runner's buffers <- the pending tokens' log-probability, rank and the top N of logits fp16 [B, vocab], the rows they
+        were picked from (nothing on a runner built without `logprobs`).  Two launches, capturable."""
+        if self.logprobs is None:
+            return
+        top = self.logprobs > 0
+        fused_ext.logprobs(logits, target=self.tokens, n_top=self.logprobs, lse=self._lse, token_logprob=self.token_logprob,
+                           rank=self.token_rank, top_tokens=self.top_tokens if top else None,
+                           top_logprobs=self.top_logprobs if top else None)
+
+    def _logprobs_of(self, logits, pred):
+        """verify() / verify_tree(): ONE call over all B * n logits rows with target = pred (None without `logprobs`)."""
+        if self.logprobs is None:
+            return None
+        return fused_ext.logprobs(logits, target=pred.reshape(-1).contiguous(), n_top=self.logprobs)
 
     # ---- prefill (context stage) ---------------------------------------------------------------------------
     def _context_bufs(self, T):
@@ -782,10 +833,14 @@ class DecodeRunner(SamplingState):
         """The context stage's tail: the last of each sequence's n rows of x -> self.x, final norm -> self.normed, lm_head, and the
         next token (arg-max, or a fresh draw on a sampling runner) -> self.tokens."""
         c = self.cfg
+        if self._score_rows is not None:
+            self._score_rows(x, n)
         self.x.copy_(x.view(self.B, n, c.hidden)[:, n - 1])
         layernorm_ops.rms_norm(self.normed, self.x, self.final_norm, c.eps, False)
         self._refill_u()
-        self._pick(torch.matmul(self.normed, self.lm_head.t()), fused_argmax=False)
+        logits = torch.matmul(self.normed, self.lm_head.t())
+        self._pick(logits, fused_argmax=False)
+        self._record_logprobs(logits)
 
     def prefill(self, prompt_len=None, tokens=None, chunk=None):
         """One context-stage pass over `prompt_len` tokens per sequence in the order of the reference's decoder
@@ -827,6 +882,72 @@ class DecodeRunner(SamplingState):
         self.lengths.zero_()
         for s in range(0, L, chunk):
             self.extend(min(chunk, L - s), tokens[:, s:s + chunk].reshape(-1))
+
+    def score(self, tokens, chunk=None, top=0, block_rows=1024):
+        """prefill(L, tokens, chunk=chunk) of tokens int64 [B, L], L >= 2 -- the same calls and the same state afterwards, byte for
+        byte -- that also scores the prompt: logprob f32 / rank int32 [B, L - 1] and, with top in 1 .. 20, top_tokens int64 /
+        top_logprobs f32 [B, L - 1, top] (else None), where entry [b, j] describes tokens[b, j + 1] given tokens[b, : j + 1] under
+        the model's RAW distribution (what the reference's prompt_logprobs asks for; perplexity() turns logprob into the accuracy
+        figure).  The context stage's rows go through final norm and lm_head in blocks of at most block_rows rows into ONE
+        reusable logits buffer [block_rows, vocab] (never [B * L, vocab]), one fused_ext.logprobs call per block; in chunked mode
+        chunk by chunk as extend() produces the rows, the target of a chunk's last row being the next chunk's first token.  The
+        result does not depend on block_rows.  Works whatever the runner's `logprobs` and `sampling` are.  -> ScoreResult."""
+        c, B, dev = self.cfg, self.B, self.device
+        if not torch.is_tensor(tokens) or tokens.dim() != 2 or tokens.shape[0] != B or tokens.dtype != torch.int64:
+            raise ValueError("score expects int64 [B, L] tokens")
+        L = int(tokens.shape[1])
+        if L < 2:
+            raise ValueError("score needs at least two tokens per sequence, got %d" % L)
+        if L + 1 > self.max_context:
+            raise ValueError("prompt length does not fit the runner's KV pools")
+        top, block_rows = int(top), int(block_rows)
+        if not 0 <= top <= fused_ext.LOGPROB_MAX_TOP:
+            raise ValueError("score takes top in 0 .. %d, got %d" % (fused_ext.LOGPROB_MAX_TOP, top))
+        if block_rows < 1:
+            raise ValueError("block_rows must be at least one row")
+        tokens = tokens.to(dev).contiguous()
+        logprob = torch.empty((B, L - 1), dtype=torch.float32, device=dev)
+        rank = torch.empty((B, L - 1), dtype=torch.int32, device=dev)
+        top_tokens = torch.empty((B, L - 1, top), dtype=torch.int64, device=dev) if top else None
+        top_logprobs = torch.empty((B, L - 1, top), dtype=torch.float32, device=dev) if top else None
+        bufs = {}      # sized by the first block, the largest
+        done = [0]     # positions per sequence that the context stage has been through
+
+        def rows(x, n):
+            s = done[0]
+            done[0] = s + n
+            k = min(n, L - 1 - s)      # the prompt's last row has no token behind it
+            if k < 1:
+                return
+            h = x.view(B, n, c.hidden)[:, :k].reshape(B * k, c.hidden)
+            tgt = tokens[:, s + 1:s + 1 + k].reshape(-1)
+            lp = torch.empty((B * k,), dtype=torch.float32, device=dev)
+            rk = torch.empty((B * k,), dtype=torch.int32, device=dev)
+            tt = torch.empty((B * k, top), dtype=torch.int64, device=dev) if top else None
+            tl = torch.empty((B * k, top), dtype=torch.float32, device=dev) if top else None
+            if not bufs:
+                m = min(block_rows, B * k)
+                bufs["normed"] = torch.empty((m, c.hidden), dtype=torch.float16, device=dev)
+                bufs["logits"] = torch.empty((m, c.vocab), dtype=torch.float16, device=dev)
+            for r0 in range(0, B * k, block_rows):
+                r1 = min(B * k, r0 + block_rows)
+                normed, logits = bufs["normed"][: r1 - r0], bufs["logits"][: r1 - r0]
+                layernorm_ops.rms_norm(normed, h[r0:r1], self.final_norm, c.eps, False)
+                torch.matmul(normed, self.lm_head.t(), out=logits)
+                fused_ext.logprobs(logits, target=tgt[r0:r1].contiguous(), n_top=top, token_logprob=lp[r0:r1], rank=rk[r0:r1],
+                                   top_tokens=tt[r0:r1] if top else None, top_logprobs=tl[r0:r1] if top else None)
+            logprob[:, s:s + k] = lp.view(B, k)
+            rank[:, s:s + k] = rk.view(B, k)
+            if top:
+                top_tokens[:, s:s + k] = tt.view(B, k, top)
+                top_logprobs[:, s:s + k] = tl.view(B, k, top)
+
+        self._score_rows = rows
+        try:
+            self.prefill(L, tokens.reshape(-1), chunk=chunk)
+        finally:
+            self._score_rows = None
+        return ScoreResult(logprob, rank, top_tokens, top_logprobs)
 
     def extend(self, new_len, tokens=None):
         """Append `new_len` tokens per sequence behind the self.lengths tokens (which may differ per sequence) already in the
@@ -885,11 +1006,18 @@ class DecodeRunner(SamplingState):
             raise ValueError("lengths + %s does not fit the runner's KV pools" % size)
         return rows, n, past_max
 
-    def _keep(self, x, normed, pred, last, counts):
+    def _keep(self, x, normed, pred, last, counts, lp=None):
         """The tail of verify() / verify_tree(): position last[b] (int64 [B, 1]) of sequence b's n scored ones is the one kept --
         its hidden state -> self.x, its normed state -> self.normed, the model's token behind it -> self.tokens -- and the
-        sequence grows by counts[b] (int32 [B])."""
+        sequence grows by counts[b] (int32 [B]).  lp (_logprobs_of's result, or None): its row of each -> the runner's buffers."""
         B, n = pred.shape
+        if lp is not None:
+            self.token_logprob.copy_(lp.token_logprob.view(B, n).gather(1, last).squeeze(1))
+            self.token_rank.copy_(lp.rank.view(B, n).gather(1, last).squeeze(1))
+            if self.logprobs > 0:
+                pick_top = last.view(B, 1, 1).expand(B, 1, self.logprobs)
+                self.top_tokens.copy_(lp.top_tokens.view(B, n, -1).gather(1, pick_top).squeeze(1))
+                self.top_logprobs.copy_(lp.top_logprobs.view(B, n, -1).gather(1, pick_top).squeeze(1))
         pick = last.view(B, 1, 1).expand(B, 1, self.cfg.hidden)
         self.x.copy_(x.view(B, n, -1).gather(1, pick).squeeze(1))
         self.normed.copy_(normed.view(B, n, -1).gather(1, pick).squeeze(1))
@@ -938,7 +1066,7 @@ class DecodeRunner(SamplingState):
         else:
             pred = torch.argmax(logits, dim=-1).view(B, n)
             m = accept_lengths(draft, pred)
-        self._keep(x, normed, pred, (m - 1).view(B, 1), m.to(torch.int32))
+        self._keep(x, normed, pred, (m - 1).view(B, 1), m.to(torch.int32), self._logprobs_of(logits, pred))
         return pred, m
 
     def verify_tree(self, tokens, parents):
@@ -971,12 +1099,13 @@ class DecodeRunner(SamplingState):
         x = self._extend_rows(n, tokens.reshape(-1), past_max, attention, rope_offsets=depth)
         normed = torch.empty_like(x)
         layernorm_ops.rms_norm(normed, x, self.final_norm, c.eps, False)
-        pred = torch.argmax(torch.matmul(normed, self.lm_head.t()), dim=-1).view(B, n)
+        logits = torch.matmul(normed, self.lm_head.t())
+        pred = torch.argmax(logits, dim=-1).view(B, n)
         path, m = accept_paths(par, tokens, pred)
         src, counts = path.to(torch.int32).contiguous(), m.to(torch.int32)
         for table in self.block_tables:
             fused_ext.kv4_compact_rows(table, self.lengths, src, counts, self.tpb, self.kl)
-        self._keep(x, normed, pred, path.gather(1, (m - 1).view(B, 1)), counts)
+        self._keep(x, normed, pred, path.gather(1, (m - 1).view(B, 1)), counts, self._logprobs_of(logits, pred))
         return pred, path, m
 
     def _all_reduce(self, buf):
