@@ -17,6 +17,7 @@
 #include "row_kernels.h"
 #include "tp_comm.h"
 #include <cstdlib>
+#include <type_traits>
 
 namespace omni {
 
@@ -348,7 +349,7 @@ template <int RT, int RV, bool FUSE_SUM, typename Src>
 __global__ __launch_bounds__(RT) void quant_v2_kernel(int8_t* __restrict__ out, Src src0,
                                                        half_t* __restrict__ sum_out, half_t* __restrict__ scale_out,
                                                        int hidden, int nv, PrefetchArgs pf) {
-  extern __shared__ __attribute__((aligned(16))) float xs[];   // [hidden] (>= RT/64 KiB, see OMNI_V2_LAUNCH)
+  extern __shared__ __attribute__((aligned(16))) float xs[];   // [hidden] (>= RT/64 KiB, see launch_rows)
   __shared__ float red[96];
   // (the rider test reads two kernel arguments: the row path's own are requested in the same batch of scalar loads -- a test
   //  on its own made every row workgroup pay a second, dependent kernarg round trip in front of its first load)
@@ -421,7 +422,7 @@ template <int RT, int RV, bool FUSE_SUM, typename Src>
 __global__ __launch_bounds__(RT) void general_norm_v2_kernel(int8_t* __restrict__ out, Src src0, const half_t* __restrict__ gamma,
                                                               half_t* __restrict__ sum_out, half_t* __restrict__ scale_out,
                                                               float eps, int hidden, int nv, PrefetchArgs pf) {
-  extern __shared__ __attribute__((aligned(16))) float xs[];   // [hidden] (>= RT/64 KiB, see OMNI_V2_LAUNCH)
+  extern __shared__ __attribute__((aligned(16))) float xs[];   // [hidden] (>= RT/64 KiB, see launch_rows)
   __shared__ float red[96];
   src0.pin();      // (as in quant_v2_kernel: one batch of scalar loads for the rider test and the row path)
   asm volatile("" ::"s"(out), "s"(gamma), "s"(sum_out), "s"(scale_out), "s"(eps), "s"(hidden), "s"(nv), "s"(pf.blocks), "s"(pf.first_block));
@@ -523,7 +524,24 @@ __global__ __launch_bounds__(RT) void rms_norm_v2_kernel(half_t* __restrict__ ou
   }
 }
 
-// dispatch helpers ------------------------------------------------------------------------------------
+// dispatch --------------------------------------------------------------------------------------------
+// Every v2 row launch is row_geometry() -- WHICH <RT, RV> -- followed by launch_rows() -- LDS bytes, prefetch riders, grid.
+// The table row_geometry() implements (first match wins; ROWS_MANY = 1024 rows, "elements" = row length):
+//
+//   family           rows           elements             geometry
+//   any              any            % 8 != 0, nv % 32 != 0 or nv > 1024   none
+//   SILU_QUANT       <  ROWS_MANY   16385 .. 32768       <512, 8>   112 - 128 KiB of LDS: raised per call
+//   any              any            > 16384              none       (first-generation kernel, or OMNI_EINVAL)
+//   TP_NORM          (<= 256)       <= 4096 / <= 8192 / more        <512, 1> / <512, 2> / <512, 4>
+//   SLAB_CHN         <  ROWS_MANY   4097 .. 8192         <512, 2>   with the BATCHED slab source, SrcSlabAddT<true, true>
+//   any              >= ROWS_MANY   <= 4096              <128, 4>   never carries prefetch riders
+//   any              >= ROWS_MANY   <= 16384             <256, 8>
+//   all but RMS_NORM <  ROWS_MANY   <= 16384             <256, 8>   only under OMNI_DECODE_RT=256 (tuning knob) and for sources
+//                                                                   that batch their fetches (Src::BATCH)
+//   any              any            <= 16384             <512, 4>   (decode-size rows only: <256, 8> covers every many-row launch)
+// Grid: one workgroup per row, plus the armed prefetch descriptor's rider workgroups (below ROWS_MANY rows, not on <128, 4>, not
+// for RMS_NORM / TP_NORM).  Dynamic LDS: the f32 copy of the row (omni_quant, which never reads it back: 8 floats), at least
+// 8 KiB when riders come along.
 static inline bool v2_ok(int hidden, int nv) {
   return hidden % 8 == 0 && nv % 32 == 0 && nv <= 1024 && hidden <= 512 * 4 * VT && (size_t)hidden * 4 <= 64 * 1024;
 }
@@ -531,7 +549,38 @@ static inline bool v2_ok(int hidden, int nv) {
 #define OMNI_ROWS_MANY 1024
 #endif
 constexpr int ROWS_MANY = OMNI_ROWS_MANY;   // from here on the narrow geometries win (measured at 16384 rows)
-// KERNEL(RT, RV) must expand to a kernel instantiation; `hidden` here is the row length that sizes the f32 LDS copy
+static inline int decode_rt() {
+  static const int v = omni_knob("OMNI_DECODE_RT", 512);
+  return v;
+}
+enum RowFamily {
+  ROWS_QUANT_NORM,   // quant_v2_kernel / general_norm_v2_kernel
+  ROWS_SILU_QUANT,   // quant_v2_kernel<..., SrcSilu>: + the large-LDS form
+  ROWS_SLAB_CHN,     // general_norm_v2_kernel over the per-channel split-K slabs: + the batched two-vector form
+  ROWS_RMS_NORM,     // rms_norm_v2_kernel: no PrefetchArgs parameter, no OMNI_DECODE_RT
+  ROWS_TP_NORM,      // tp_add_norm_v2_kernel: 512 threads, as many vectors as the row needs (the source batches its requests: an
+                     // unused vector would re-read element 0 of every peer)
+};
+struct RowGeom { int rt, rv; };   // rt == 0: no v2 geometry covers the row
+static inline RowGeom row_geometry(RowFamily fam, int rows, int elems, int nv, bool batched) {
+  const bool many = rows >= ROWS_MANY;
+  if (!v2_ok(elems, nv)) {
+    // rows of 16384 < d <= 32768 (Llama-2/3-70B's intermediate size at TP = 1: 28672), one workgroup per CU (a decode batch has
+    // fewer rows than the chip has CUs; the one-thread-per-32-columns kernel took 13.6 us per layer at bs = 128, profiles/r05_f).
+    // Decode-size launches only: many rows at one 512-thread workgroup per CU keep the first-generation kernel -- ADVICE r5
+    const bool large = fam == ROWS_SILU_QUANT && !many && elems > 512 * 4 * VT && elems <= 512 * 8 * VT && elems % 8 == 0 &&
+                       nv % 32 == 0 && nv <= 1024;
+    return large ? RowGeom{512, 8} : RowGeom{0, 0};
+  }
+  if (fam == ROWS_TP_NORM) return RowGeom{512, elems <= 512 * VT ? 1 : elems <= 512 * 2 * VT ? 2 : 4};
+  // decode-size rows of 4097 .. 8192 columns (Llama-2-70B): two vectors per thread with BATCHED requests -- the unbatched
+  // source made the second vector's slab loads a second memory round trip of the row chain
+  if (fam == ROWS_SLAB_CHN && !many && elems > 512 * VT && elems <= 512 * 2 * VT) return RowGeom{512, 2};
+  if (many && elems <= 128 * 4 * VT) return RowGeom{128, 4};
+  if ((many || (fam != ROWS_RMS_NORM && batched && decode_rt() == 256)) && elems <= 256 * 8 * VT) return RowGeom{256, 8};
+  return RowGeom{512, 4};
+}
+
 // One-shot prefetch descriptor (omni_prefetch_arm_gemm, qgemm_plan.hip): consumed by the next v2 quant /
 // general-norm launch.
 PrefetchArgs take_armed_prefetch();
@@ -541,38 +590,49 @@ static inline PrefetchArgs take_prefetch(int tokens) {
   if (tokens >= ROWS_MANY) pf.blocks = 0;    // many-row launches are bandwidth-bound themselves: nothing idles
   return pf;
 }
-// (kernels without a PrefetchArgs parameter)
-#define OMNI_V2_LAUNCH_PLAIN(KERNEL, tokens, hidden, elems, ...)                                                \
-  do {                                                                                                          \
-    const size_t lds_ = (size_t)(hidden) * sizeof(float);                                                       \
-    if ((tokens) >= ROWS_MANY && (elems) <= 128 * 4 * VT)                                                       \
-      hipLaunchKernelGGL((KERNEL(128, 4)), dim3(tokens), dim3(128), lds_, (hipStream_t)stream, __VA_ARGS__);    \
-    else if ((tokens) >= ROWS_MANY && (elems) <= 256 * 8 * VT)                                                  \
-      hipLaunchKernelGGL((KERNEL(256, 8)), dim3(tokens), dim3(256), lds_, (hipStream_t)stream, __VA_ARGS__);    \
-    else                                                                                                        \
-      hipLaunchKernelGGL((KERNEL(512, 4)), dim3(tokens), dim3(512), lds_, (hipStream_t)stream, __VA_ARGS__);    \
-  } while (0)
-// quant / general-norm kernels: the armed prefetch descriptor rides along as extra workgroups (decode-size launches).
-// OMNI_DECODE_RT=256 (tuning knob) runs decode-size rows of sources that batch their loads on 256 threads instead of 512.
-static const bool v2_batched = true;     // shadowed by `false` at the launch sites of sources that fetch per vector
-static inline int decode_rt() {
-  static const int v = omni_knob("OMNI_DECODE_RT", 512);
-  return v;
+
+// The geometries a kernel family is instantiated at (launch_rows() instantiates nothing else)
+template <int RT_, int RV_> struct Geo { static constexpr int RT = RT_, RV = RV_; };
+template <typename... Gs> struct GeoList {};
+typedef GeoList<Geo<128, 4>, Geo<256, 8>, Geo<512, 4>> GeosRow;
+typedef GeoList<Geo<128, 4>, Geo<256, 8>, Geo<512, 4>, Geo<512, 8>> GeosSilu;
+typedef GeoList<Geo<512, 2>> GeosSlabBatched;
+typedef GeoList<Geo<512, 1>, Geo<512, 2>, Geo<512, 4>> GeosTp;
+
+// Launches kernel_of(Geo<g.rt, g.rv>)(args...[, pf]) with one workgroup per row and lds_floats f32 of dynamic LDS.
+// RIDERS (kernels whose last parameter is PrefetchArgs): the armed prefetch descriptor is consumed here and rides along as extra
+// workgroups behind the rows -- except on <128, 4> -- with at least 8 KiB of LDS (1 KiB of LDS-DMA target per wave).
+// Without RIDERS an armed descriptor is left alone.
+template <bool RIDERS, typename... Gs, typename KernelOf, typename... Args>
+static int launch_rows(GeoList<Gs...>, RowGeom g, int rows, size_t lds_floats, void* stream, KernelOf kernel_of, const Args&... args) {
+  PrefetchArgs pf{};
+  size_t lds = lds_floats * sizeof(float);
+  if constexpr (RIDERS) {
+    pf = take_prefetch(rows);
+    if (pf.blocks > 0 && lds < 8 * 1024) lds = 8 * 1024;
+  }
+  const int grid = rows + (g.rt == 128 ? 0 : pf.blocks);
+  bool launched = false;
+  auto launch = [&](auto geo) {
+    auto kern = kernel_of(geo);
+    // (dynamic LDS beyond 64 KiB is an opt-in per kernel AND per device: set on every call, like sparse_utils.hip does --
+    //  a process-wide flag missed the second device and raced between threads)
+    if constexpr ((size_t)geo.RT * geo.RV * VT * sizeof(float) > 64 * 1024)
+      if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024) != hipSuccess)
+        return;
+    if constexpr (RIDERS) hipLaunchKernelGGL(kern, dim3(grid), dim3(geo.RT), lds, (hipStream_t)stream, args..., pf);
+    else hipLaunchKernelGGL(kern, dim3(grid), dim3(geo.RT), lds, (hipStream_t)stream, args...);
+    launched = true;
+  };
+  // (contract: every geometry row_geometry() can return for the caller's family is in Gs -- a new table row needs its list
+  //  entry; a geometry outside the list launches nothing and reports OMNI_ELAUNCH, as a refused LDS attribute does)
+  (void)(... || (g.rt == Gs::RT && g.rv == Gs::RV && (launch(Gs{}), true)));
+  return launched ? omni_launch_status() : OMNI_ELAUNCH;
 }
-#define OMNI_V2_LAUNCH(KERNEL, tokens, hidden, elems, ...)                                                      \
-  do {                                                                                                          \
-    const PrefetchArgs pf_ = take_prefetch(tokens);                                                             \
-    size_t lds_ = (size_t)(hidden) * sizeof(float);                                                             \
-    if (pf_.blocks > 0 && lds_ < 8 * 1024) lds_ = 8 * 1024;   /* 1 KiB of LDS-DMA target per wave */            \
-    if ((tokens) >= ROWS_MANY && (elems) <= 128 * 4 * VT)                                                       \
-      hipLaunchKernelGGL((KERNEL(128, 4)), dim3(tokens), dim3(128), lds_, (hipStream_t)stream, __VA_ARGS__, pf_);  \
-    else if (((tokens) >= ROWS_MANY || (decode_rt() == 256 && v2_batched)) && (elems) <= 256 * 8 * VT)          \
-      hipLaunchKernelGGL((KERNEL(256, 8)), dim3((tokens) + pf_.blocks), dim3(256), lds_, (hipStream_t)stream,   \
-                         __VA_ARGS__, pf_);                                                                     \
-    else                                                                                                        \
-      hipLaunchKernelGGL((KERNEL(512, 4)), dim3((tokens) + pf_.blocks), dim3(512), lds_, (hipStream_t)stream,   \
-                         __VA_ARGS__, pf_);                                                                     \
-  } while (0)
+// f(std::true_type / std::false_type) for "the caller passed this optional pointer": the kernels' FUSE_SUM argument from the sum
+// pointer (also: the zero-term epilogue from the zero-term pointer)
+template <typename Fn>
+static inline int with_flag(const void* ptr, Fn f) { return ptr ? f(std::true_type{}) : f(std::false_type{}); }
 
 static inline int norm_block(int hidden, bool round32) {
   int b = hidden < NT_MAX ? hidden : NT_MAX;
@@ -584,24 +644,31 @@ static inline int norm_block(int hidden, bool round32) {
 
 using namespace omni;
 
+// omni_quant (sum_f16 == NULL) / omni_quant_fuse_sum
+static int quant_rows(void* out_i8, const void* in_f16, void* sum_f16, void* scale_f16, int tokens, int hidden,
+                      size_t lds_floats, void* stream) {
+  const int nv = norm_block(hidden, false);
+  const RowGeom g = row_geometry(ROWS_QUANT_NORM, tokens, hidden, nv, SrcPlain::BATCH);
+  return with_flag(sum_f16, [&](auto fuse) {
+    constexpr bool FS = decltype(fuse)::value;
+    if (g.rt)
+      return launch_rows<true>(GeosRow{}, g, tokens, lds_floats, stream,
+                               [](auto geo) { return quant_v2_kernel<geo.RT, geo.RV, FS, SrcPlain>; }, (int8_t*)out_i8,
+                               SrcPlain{(const half_t*)in_f16, hidden}, (half_t*)sum_f16, (half_t*)scale_f16, hidden, nv);
+    (void)take_armed_prefetch();   // this geometry cannot carry the L2 prefetch: drop an armed descriptor instead of leaving it for a later launch
+    hipLaunchKernelGGL((quant_kernel<FS>), dim3(tokens), dim3(nv), 0, (hipStream_t)stream, (int8_t*)out_i8,
+                       (const half_t*)in_f16, (half_t*)sum_f16, (half_t*)scale_f16, hidden);
+    return omni_launch_status();
+  });
+}
+
 extern "C" int omni_quant(void* out_i8, const void* in_f16, void* scale_f16, int tokens, int hidden,
                           void* stream) {
   if (!out_i8 || !in_f16 || !scale_f16 || tokens < 0 || hidden < 1) return OMNI_EINVAL;
   if (hidden % 32 != 0) return OMNI_EINVAL;  // reference geometry: block = min(hidden,1024)
   if (tokens == 0) return OMNI_OK;
-  const int nv = norm_block(hidden, false);
-  if (v2_ok(hidden, nv)) {
-    #undef KQ_
-    #define KQ_(RT_, RV_) quant_v2_kernel<RT_, RV_, false, SrcPlain>
-    OMNI_V2_LAUNCH(KQ_, tokens, 8, hidden, (int8_t*)out_i8, SrcPlain{(const half_t*)in_f16, hidden},
-                   (half_t*)nullptr, (half_t*)scale_f16, hidden, nv);
-    return omni_launch_status();
-  }
-  (void)take_armed_prefetch();   // this geometry cannot carry the L2 prefetch: drop an armed descriptor instead of leaving it for a later launch
-  hipLaunchKernelGGL((quant_kernel<false>), dim3(tokens), dim3(norm_block(hidden, false)), 0,
-                     (hipStream_t)stream, (int8_t*)out_i8, (const half_t*)in_f16, (half_t*)nullptr,
-                     (half_t*)scale_f16, hidden);
-  return omni_launch_status();
+  // (without the row sum nothing reads the f32 LDS copy of the row: LDS for 8 floats, not `hidden`)
+  return quant_rows(out_i8, in_f16, nullptr, scale_f16, tokens, hidden, 8, stream);
 }
 
 extern "C" int omni_quant_fuse_sum(void* out_i8, const void* in_f16, void* sum_f16, void* scale_f16,
@@ -609,19 +676,7 @@ extern "C" int omni_quant_fuse_sum(void* out_i8, const void* in_f16, void* sum_f
   if (!out_i8 || !in_f16 || !sum_f16 || !scale_f16 || tokens < 0 || hidden < 1) return OMNI_EINVAL;
   if (hidden % 32 != 0) return OMNI_EINVAL;
   if (tokens == 0) return OMNI_OK;
-  const int nv = norm_block(hidden, false);
-  if (v2_ok(hidden, nv)) {
-    #undef KQ_
-    #define KQ_(RT_, RV_) quant_v2_kernel<RT_, RV_, true, SrcPlain>
-    OMNI_V2_LAUNCH(KQ_, tokens, hidden, hidden, (int8_t*)out_i8, SrcPlain{(const half_t*)in_f16, hidden},
-                   (half_t*)sum_f16, (half_t*)scale_f16, hidden, nv);
-    return omni_launch_status();
-  }
-  (void)take_armed_prefetch();   // this geometry cannot carry the L2 prefetch: drop an armed descriptor instead of leaving it for a later launch
-  hipLaunchKernelGGL((quant_kernel<true>), dim3(tokens), dim3(norm_block(hidden, false)), 0,
-                     (hipStream_t)stream, (int8_t*)out_i8, (const half_t*)in_f16, (half_t*)sum_f16,
-                     (half_t*)scale_f16, hidden);
-  return omni_launch_status();
+  return quant_rows(out_i8, in_f16, sum_f16, scale_f16, tokens, hidden, hidden, stream);
 }
 
 extern "C" int omni_rms_norm(void* out_f16, const void* in_f16, const void* weight_f16, float eps,
@@ -629,20 +684,36 @@ extern "C" int omni_rms_norm(void* out_f16, const void* in_f16, const void* weig
   if (!out_f16 || !in_f16 || !weight_f16 || tokens < 0 || hidden < 1) return OMNI_EINVAL;
   if (hidden % 32 != 0 || hidden > VPT * NT_MAX) return OMNI_EINVAL;
   if (tokens == 0) return OMNI_OK;
-  {
-    const int nv = norm_block(hidden, false);
-    if (v2_ok(hidden, nv)) {
-      #undef KQ_
-      #define KQ_(RT_, RV_) rms_norm_v2_kernel<RT_, RV_>
-      OMNI_V2_LAUNCH_PLAIN(KQ_, tokens, hidden, hidden, (half_t*)out_f16, SrcPlain{(const half_t*)in_f16, hidden},
-                           (const half_t*)weight_f16, eps, hidden, nv);
-      return omni_launch_status();
-    }
-  }
-  hipLaunchKernelGGL(rms_norm_kernel, dim3(tokens), dim3(norm_block(hidden, false)), 0,
-                     (hipStream_t)stream, (half_t*)out_f16, (const half_t*)in_f16,
-                     (const half_t*)weight_f16, eps, hidden);
+  const int nv = norm_block(hidden, false);
+  const RowGeom g = row_geometry(ROWS_RMS_NORM, tokens, hidden, nv, SrcPlain::BATCH);
+  if (g.rt)
+    return launch_rows<false>(GeosRow{}, g, tokens, hidden, stream,
+                              [](auto geo) { return rms_norm_v2_kernel<geo.RT, geo.RV, SrcPlain>; }, (half_t*)out_f16,
+                              SrcPlain{(const half_t*)in_f16, hidden}, (const half_t*)weight_f16, eps, hidden, nv);
+  hipLaunchKernelGGL(rms_norm_kernel, dim3(tokens), dim3(nv), 0, (hipStream_t)stream, (half_t*)out_f16,
+                     (const half_t*)in_f16, (const half_t*)weight_f16, eps, hidden);
   return omni_launch_status();
+}
+
+// rms_norm_general[_fuse_sum] of a plain row (Src = SrcPlain), or with the fused residual add in front of it (SrcAdd).
+// sum_f16 == NULL: no row sum.  in_f16 / delta_f16: the source's own pointers, for the first-generation kernel
+template <typename Src>
+static int general_norm_rows(const Src& src, void* out_i8, void* in_f16, const void* delta_f16, const void* weight_f16,
+                             void* sum_f16, void* scale_f16, float eps, int tokens, int hidden, void* stream) {
+  const int nv = norm_block(hidden, true);
+  const RowGeom g = row_geometry(ROWS_QUANT_NORM, tokens, hidden, nv, Src::BATCH);
+  return with_flag(sum_f16, [&](auto fuse) {
+    constexpr bool FS = decltype(fuse)::value;
+    if (g.rt)
+      return launch_rows<true>(GeosRow{}, g, tokens, hidden, stream,
+                               [](auto geo) { return general_norm_v2_kernel<geo.RT, geo.RV, FS, Src>; }, (int8_t*)out_i8, src,
+                               (const half_t*)weight_f16, (half_t*)sum_f16, (half_t*)scale_f16, eps, hidden, nv);
+    (void)take_armed_prefetch();   // this geometry cannot carry the L2 prefetch: drop an armed descriptor instead of leaving it for a later launch
+    hipLaunchKernelGGL((general_norm_quant_kernel<FS, std::is_same<Src, SrcAdd>::value>), dim3(tokens), dim3(nv), 0,
+                       (hipStream_t)stream, (int8_t*)out_i8, (half_t*)in_f16, (const half_t*)delta_f16,
+                       (const half_t*)weight_f16, (half_t*)sum_f16, (half_t*)scale_f16, eps, hidden);
+    return omni_launch_status();
+  });
 }
 
 extern "C" int omni_rms_norm_general(void* out_i8, const void* in_f16, const void* weight_f16,
@@ -651,22 +722,8 @@ extern "C" int omni_rms_norm_general(void* out_i8, const void* in_f16, const voi
   if (!out_i8 || !in_f16 || !weight_f16 || !scale_f16 || tokens < 0 || hidden < 1) return OMNI_EINVAL;
   if (hidden > VPT * NT_MAX) return OMNI_EINVAL;
   if (tokens == 0) return OMNI_OK;
-  {
-    const int nv = norm_block(hidden, true);
-    if (v2_ok(hidden, nv)) {
-      #undef KQ_
-      #define KQ_(RT_, RV_) general_norm_v2_kernel<RT_, RV_, false, SrcPlain>
-      OMNI_V2_LAUNCH(KQ_, tokens, hidden, hidden, (int8_t*)out_i8,
-                     SrcPlain{(const half_t*)in_f16, hidden}, (const half_t*)weight_f16, (half_t*)nullptr,
-                     (half_t*)scale_f16, eps, hidden, nv);
-      return omni_launch_status();
-    }
-  }
-  (void)take_armed_prefetch();   // this geometry cannot carry the L2 prefetch: drop an armed descriptor instead of leaving it for a later launch
-  hipLaunchKernelGGL((general_norm_quant_kernel<false, false>), dim3(tokens), dim3(norm_block(hidden, true)),
-                     0, (hipStream_t)stream, (int8_t*)out_i8, (half_t*)in_f16, (const half_t*)nullptr,
-                     (const half_t*)weight_f16, (half_t*)nullptr, (half_t*)scale_f16, eps, hidden);
-  return omni_launch_status();
+  return general_norm_rows(SrcPlain{(const half_t*)in_f16, hidden}, out_i8, const_cast<void*>(in_f16), nullptr, weight_f16, nullptr,
+                           scale_f16, eps, tokens, hidden, stream);
 }
 
 extern "C" int omni_rms_norm_general_fuse_sum(void* out_i8, const void* in_f16,
@@ -677,22 +734,8 @@ extern "C" int omni_rms_norm_general_fuse_sum(void* out_i8, const void* in_f16,
     return OMNI_EINVAL;
   if (hidden > VPT * NT_MAX) return OMNI_EINVAL;
   if (tokens == 0) return OMNI_OK;
-  {
-    const int nv = norm_block(hidden, true);
-    if (v2_ok(hidden, nv)) {
-      #undef KQ_
-      #define KQ_(RT_, RV_) general_norm_v2_kernel<RT_, RV_, true, SrcPlain>
-      OMNI_V2_LAUNCH(KQ_, tokens, hidden, hidden, (int8_t*)out_i8,
-                     SrcPlain{(const half_t*)in_f16, hidden}, (const half_t*)weight_f16, (half_t*)sum_f16,
-                     (half_t*)scale_f16, eps, hidden, nv);
-      return omni_launch_status();
-    }
-  }
-  (void)take_armed_prefetch();   // this geometry cannot carry the L2 prefetch: drop an armed descriptor instead of leaving it for a later launch
-  hipLaunchKernelGGL((general_norm_quant_kernel<true, false>), dim3(tokens), dim3(norm_block(hidden, true)),
-                     0, (hipStream_t)stream, (int8_t*)out_i8, (half_t*)in_f16, (const half_t*)nullptr,
-                     (const half_t*)weight_f16, (half_t*)sum_f16, (half_t*)scale_f16, eps, hidden);
-  return omni_launch_status();
+  return general_norm_rows(SrcPlain{(const half_t*)in_f16, hidden}, out_i8, const_cast<void*>(in_f16), nullptr, weight_f16, sum_f16,
+                           scale_f16, eps, tokens, hidden, stream);
 }
 
 extern "C" int omni_silu_and_mul(void* out_f16, const void* in_f16, int tokens, int d, void* stream) {
@@ -756,35 +799,8 @@ extern "C" int omni_add_rms_norm_general_fuse_sum(void* out_i8, void* residual_f
     return OMNI_EINVAL;
   if (hidden > VPT * NT_MAX) return OMNI_EINVAL;
   if (tokens == 0) return OMNI_OK;
-  {
-    const int nv = norm_block(hidden, true);
-    if (v2_ok(hidden, nv)) {
-      if (sum_f16) {
-        #undef KQ_
-        #define KQ_(RT_, RV_) general_norm_v2_kernel<RT_, RV_, true, SrcAdd>
-        OMNI_V2_LAUNCH(KQ_, tokens, hidden, hidden, (int8_t*)out_i8,
-                       SrcAdd{(half_t*)residual_f16, (const half_t*)delta_f16, hidden}, (const half_t*)weight_f16,
-                       (half_t*)sum_f16, (half_t*)scale_f16, eps, hidden, nv);
-      } else {
-        #undef KQ_
-        #define KQ_(RT_, RV_) general_norm_v2_kernel<RT_, RV_, false, SrcAdd>
-        OMNI_V2_LAUNCH(KQ_, tokens, hidden, hidden, (int8_t*)out_i8,
-                       SrcAdd{(half_t*)residual_f16, (const half_t*)delta_f16, hidden}, (const half_t*)weight_f16,
-                       (half_t*)nullptr, (half_t*)scale_f16, eps, hidden, nv);
-      }
-      return omni_launch_status();
-    }
-  }
-  (void)take_armed_prefetch();
-  if (sum_f16)
-    hipLaunchKernelGGL((general_norm_quant_kernel<true, true>), dim3(tokens), dim3(norm_block(hidden, true)),
-                       0, (hipStream_t)stream, (int8_t*)out_i8, (half_t*)residual_f16, (const half_t*)delta_f16,
-                       (const half_t*)weight_f16, (half_t*)sum_f16, (half_t*)scale_f16, eps, hidden);
-  else
-    hipLaunchKernelGGL((general_norm_quant_kernel<false, true>), dim3(tokens), dim3(norm_block(hidden, true)),
-                       0, (hipStream_t)stream, (int8_t*)out_i8, (half_t*)residual_f16, (const half_t*)delta_f16,
-                       (const half_t*)weight_f16, (half_t*)nullptr, (half_t*)scale_f16, eps, hidden);
-  return omni_launch_status();
+  return general_norm_rows(SrcAdd{(half_t*)residual_f16, (const half_t*)delta_f16, hidden}, out_i8, residual_f16, delta_f16, weight_f16,
+                           sum_f16, scale_f16, eps, tokens, hidden, stream);
 }
 
 extern "C" int omni_silu_mul_quant_fuse_sum(void* out_i8, const void* in_f16, void* sum_f16, void* scale_f16,
@@ -793,58 +809,19 @@ extern "C" int omni_silu_mul_quant_fuse_sum(void* out_i8, const void* in_f16, vo
   if (!out_i8 || !in_f16 || !scale_f16 || tokens < 0 || d < 1) return OMNI_EINVAL;
   if (d % 32 != 0) return OMNI_EINVAL;
   if (tokens == 0) return OMNI_OK;
-  {
-    const int nv = norm_block(d, false);
-    if (v2_ok(d, nv)) {
-      if (sum_f16) {
-        #undef KQ_
-        #define KQ_(RT_, RV_) quant_v2_kernel<RT_, RV_, true, SrcSilu>
-        OMNI_V2_LAUNCH(KQ_, tokens, d, d, (int8_t*)out_i8, SrcSilu{(const half_t*)in_f16, d},
-                       (half_t*)sum_f16, (half_t*)scale_f16, d, nv);
-      } else {
-        #undef KQ_
-        #define KQ_(RT_, RV_) quant_v2_kernel<RT_, RV_, false, SrcSilu>
-        OMNI_V2_LAUNCH(KQ_, tokens, d, d, (int8_t*)out_i8, SrcSilu{(const half_t*)in_f16, d},
-                       (half_t*)nullptr, (half_t*)scale_f16, d, nv);
-      }
-      return omni_launch_status();
-    }
-  }
-  // Rows of 16384 < d <= 32768 (Llama-2/3-70B's intermediate size at TP = 1: 28672): the <512, 8> geometry, 112 KiB of LDS for
-  // the f32 row copy (one workgroup per CU; a decode batch has fewer rows than the chip has CUs).  The one-thread-per-32-columns
-  // kernel below took 13.6 us per layer at bs = 128 (128 workgroups, a serial loop of 56 vectors per thread; profiles/r05_f).
-  {
-    const int nv = norm_block(d, false);
-    // decode-size launches only (measured there; a many-row launch would run ONE 512-thread workgroup per CU at 112 - 128 KiB
-    // of LDS: those keep the kernel below -- ADVICE r5)
-    if (tokens < ROWS_MANY && d > 512 * 4 * VT && d <= 512 * 8 * VT && d % 8 == 0 && nv % 32 == 0 && nv <= 1024) {
-      const PrefetchArgs pf = take_prefetch(tokens);
-      const size_t lds = (size_t)d * sizeof(float);
-      bool raised_ok = true;
-      auto launch = [&](auto kern, half_t* sum) {
-        // (dynamic LDS beyond 64 KiB is an opt-in per kernel AND per device: set on every call, like sparse_utils.hip does --
-        //  a process-wide flag missed the second device and raced between threads)
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024) != hipSuccess) {
-          raised_ok = false;
-          return;
-        }
-        hipLaunchKernelGGL(kern, dim3(tokens + pf.blocks), dim3(512), lds, (hipStream_t)stream, (int8_t*)out_i8,
-                           SrcSilu{(const half_t*)in_f16, d}, sum, (half_t*)scale_f16, d, nv, pf);
-      };
-      if (sum_f16) launch(quant_v2_kernel<512, 8, true, SrcSilu>, (half_t*)sum_f16);
-      else launch(quant_v2_kernel<512, 8, false, SrcSilu>, (half_t*)nullptr);
-      return raised_ok ? omni_launch_status() : OMNI_ELAUNCH;
-    }
-  }
-  (void)take_armed_prefetch();
-  // row lengths outside every v2 geometry
-  if (sum_f16)
-    hipLaunchKernelGGL(silu_mul_quant_kernel<true>, dim3(tokens), dim3(norm_block(d, false)), 0, (hipStream_t)stream,
-                       (int8_t*)out_i8, (const half_t*)in_f16, (half_t*)sum_f16, (half_t*)scale_f16, d);
-  else
-    hipLaunchKernelGGL(silu_mul_quant_kernel<false>, dim3(tokens), dim3(norm_block(d, false)), 0, (hipStream_t)stream,
-                       (int8_t*)out_i8, (const half_t*)in_f16, (half_t*)nullptr, (half_t*)scale_f16, d);
-  return omni_launch_status();
+  const int nv = norm_block(d, false);
+  const RowGeom g = row_geometry(ROWS_SILU_QUANT, tokens, d, nv, SrcSilu::BATCH);
+  return with_flag(sum_f16, [&](auto fuse) {
+    constexpr bool FS = decltype(fuse)::value;
+    if (g.rt)
+      return launch_rows<true>(GeosSilu{}, g, tokens, d, stream, [](auto geo) { return quant_v2_kernel<geo.RT, geo.RV, FS, SrcSilu>; },
+                               (int8_t*)out_i8, SrcSilu{(const half_t*)in_f16, d}, (half_t*)sum_f16, (half_t*)scale_f16, d, nv);
+    (void)take_armed_prefetch();
+    // row lengths outside every v2 geometry
+    hipLaunchKernelGGL(silu_mul_quant_kernel<FS>, dim3(tokens), dim3(nv), 0, (hipStream_t)stream, (int8_t*)out_i8,
+                       (const half_t*)in_f16, (half_t*)sum_f16, (half_t*)scale_f16, d);
+    return omni_launch_status();
+  });
 }
 
 extern "C" int omni_splitk_add_rms_norm_general_fuse_sum(void* out_i8, void* residual_f16, const void* slab_i32, int sk,
@@ -858,27 +835,16 @@ extern "C" int omni_splitk_add_rms_norm_general_fuse_sum(void* out_i8, void* res
   const int nv = norm_block(hidden, true);
   if (!v2_ok(hidden, nv)) return OMNI_EINVAL;
   if (tokens == 0) return OMNI_OK;
-  SrcSlabAddChn src{(half_t*)residual_f16, (const int32_t*)slab_i32, (size_t)tokens * hidden, sk, hidden,
-                    (const half_t*)wscales_f16, (const half_t*)w_szs_f16, (const half_t*)ascales_in_f16,
-                    (const half_t*)a_ssums_in_f16, (half_t)0.0f, (half_t)0.0f};
-  if (tokens < ROWS_MANY && hidden > 512 * VT && hidden <= 512 * 2 * VT) {
-    // decode-size rows of 4097 .. 8192 columns (Llama-2-70B): two vectors per thread with BATCHED requests -- the unbatched
-    // source made the second vector's slab loads a second memory round trip of the row chain
-    typedef SrcSlabAddT<true, true> SrcB;
-    SrcB srcb{src.res, src.slab, src.sstride, src.sk, src.stride, src.wscales, src.wsz, src.ascales, src.asum, (half_t)0.0f, (half_t)0.0f};
-    const PrefetchArgs pf = take_prefetch(tokens);
-    size_t lds = (size_t)hidden * sizeof(float);
-    if (pf.blocks > 0 && lds < 8 * 1024) lds = 8 * 1024;
-    hipLaunchKernelGGL((general_norm_v2_kernel<512, 2, true, SrcB>), dim3(tokens + pf.blocks), dim3(512), lds, (hipStream_t)stream,
-                       (int8_t*)out_i8, srcb, (const half_t*)weight_f16, (half_t*)sum_f16, (half_t*)scale_f16, eps, hidden, nv, pf);
-    return omni_launch_status();
-  }
-  const bool v2_batched = false;
-  #undef KQ_
-  #define KQ_(RT_, RV_) general_norm_v2_kernel<RT_, RV_, true, SrcSlabAddChn>
-  OMNI_V2_LAUNCH(KQ_, tokens, hidden, hidden, (int8_t*)out_i8, src,
-                 (const half_t*)weight_f16, (half_t*)sum_f16, (half_t*)scale_f16, eps, hidden, nv);
-  return omni_launch_status();
+  const RowGeom g = row_geometry(ROWS_SLAB_CHN, tokens, hidden, nv, SrcSlabAddChn::BATCH);
+  auto launch = [&](auto batch, auto geos) {   // <512, 2> exists with the batched source only, the other three with the unbatched one
+    typedef SrcSlabAddT<true, decltype(batch)::value> Src;
+    const Src src{(half_t*)residual_f16, (const int32_t*)slab_i32, (size_t)tokens * hidden, sk, hidden,
+                  (const half_t*)wscales_f16, (const half_t*)w_szs_f16, (const half_t*)ascales_in_f16,
+                  (const half_t*)a_ssums_in_f16, (half_t)0.0f, (half_t)0.0f};
+    return launch_rows<true>(geos, g, tokens, hidden, stream, [](auto geo) { return general_norm_v2_kernel<geo.RT, geo.RV, true, Src>; },
+                             (int8_t*)out_i8, src, (const half_t*)weight_f16, (half_t*)sum_f16, (half_t*)scale_f16, eps, hidden, nv);
+  };
+  return g.rv == 2 ? launch(std::true_type{}, GeosSlabBatched{}) : launch(std::false_type{}, GeosRow{});
 }
 
 // The same for the W8A8 GEMM (omni_w8a8_gemm_partial): epilogue h(f32(acc) * (wscales[n] * ascales[m])), no zero term.
@@ -893,22 +859,16 @@ extern "C" int omni_splitk_w8_add_rms_norm_general_fuse_sum(void* out_i8, void* 
   const int nv = norm_block(hidden, true);
   if (!v2_ok(hidden, nv)) return OMNI_EINVAL;
   if (tokens == 0) return OMNI_OK;
-  SrcSlabAddW8 src{(half_t*)residual_f16, (const int32_t*)slab_i32, (size_t)tokens * hidden, sk, hidden,
-                   (const half_t*)wscales_f16, (const half_t*)nullptr, (const half_t*)ascales_in_f16,
-                   (const half_t*)nullptr, (half_t)0.0f, (half_t)0.0f};
-  const bool v2_batched = false;
-  if (sum_f16) {
-    #undef KQ_
-    #define KQ_(RT_, RV_) general_norm_v2_kernel<RT_, RV_, true, SrcSlabAddW8>
-    OMNI_V2_LAUNCH(KQ_, tokens, hidden, hidden, (int8_t*)out_i8, src,
-                   (const half_t*)weight_f16, (half_t*)sum_f16, (half_t*)scale_f16, eps, hidden, nv);
-  } else {
-    #undef KQ_
-    #define KQ_(RT_, RV_) general_norm_v2_kernel<RT_, RV_, false, SrcSlabAddW8>
-    OMNI_V2_LAUNCH(KQ_, tokens, hidden, hidden, (int8_t*)out_i8, src,
-                   (const half_t*)weight_f16, (half_t*)nullptr, (half_t*)scale_f16, eps, hidden, nv);
-  }
-  return omni_launch_status();
+  const SrcSlabAddW8 src{(half_t*)residual_f16, (const int32_t*)slab_i32, (size_t)tokens * hidden, sk, hidden,
+                         (const half_t*)wscales_f16, (const half_t*)nullptr, (const half_t*)ascales_in_f16,
+                         (const half_t*)nullptr, (half_t)0.0f, (half_t)0.0f};
+  const RowGeom g = row_geometry(ROWS_QUANT_NORM, tokens, hidden, nv, SrcSlabAddW8::BATCH);
+  return with_flag(sum_f16, [&](auto fuse) {
+    constexpr bool FS = decltype(fuse)::value;
+    return launch_rows<true>(GeosRow{}, g, tokens, hidden, stream,
+                             [](auto geo) { return general_norm_v2_kernel<geo.RT, geo.RV, FS, SrcSlabAddW8>; }, (int8_t*)out_i8, src,
+                             (const half_t*)weight_f16, (half_t*)sum_f16, (half_t*)scale_f16, eps, hidden, nv);
+  });
 }
 
 // Fused extension: the LAST decoder layer's down projection deferred into the model's final norm -- residual += fp16(GEMM
@@ -924,22 +884,15 @@ extern "C" int omni_splitk_add_rms_norm(void* out_f16, void* residual_f16, const
   const int nv = norm_block(hidden, false);
   if (!v2_ok(hidden, nv)) return OMNI_EINVAL;
   if (tokens == 0) return OMNI_OK;
-  if (w_szs_f16) {
-    SrcSlabAddChn src{(half_t*)residual_f16, (const int32_t*)slab_i32, (size_t)tokens * hidden, sk, hidden,
-                      (const half_t*)wscales_f16, (const half_t*)w_szs_f16, (const half_t*)ascales_in_f16,
-                      (const half_t*)a_ssums_in_f16, (half_t)0.0f, (half_t)0.0f};
-    #undef KQ_
-    #define KQ_(RT_, RV_) rms_norm_v2_kernel<RT_, RV_, SrcSlabAddChn>
-    OMNI_V2_LAUNCH_PLAIN(KQ_, tokens, hidden, hidden, (half_t*)out_f16, src, (const half_t*)weight_f16, eps, hidden, nv);
-  } else {
-    SrcSlabAddW8 src{(half_t*)residual_f16, (const int32_t*)slab_i32, (size_t)tokens * hidden, sk, hidden,
-                     (const half_t*)wscales_f16, (const half_t*)nullptr, (const half_t*)ascales_in_f16,
-                     (const half_t*)nullptr, (half_t)0.0f, (half_t)0.0f};
-    #undef KQ_
-    #define KQ_(RT_, RV_) rms_norm_v2_kernel<RT_, RV_, SrcSlabAddW8>
-    OMNI_V2_LAUNCH_PLAIN(KQ_, tokens, hidden, hidden, (half_t*)out_f16, src, (const half_t*)weight_f16, eps, hidden, nv);
-  }
-  return omni_launch_status();
+  return with_flag(w_szs_f16, [&](auto zp) {
+    typedef SrcSlabAddT<decltype(zp)::value> Src;
+    const RowGeom g = row_geometry(ROWS_RMS_NORM, tokens, hidden, nv, Src::BATCH);
+    const Src src{(half_t*)residual_f16, (const int32_t*)slab_i32, (size_t)tokens * hidden, sk, hidden,
+                  (const half_t*)wscales_f16, (const half_t*)w_szs_f16, (const half_t*)ascales_in_f16,
+                  (const half_t*)a_ssums_in_f16, (half_t)0.0f, (half_t)0.0f};
+    return launch_rows<false>(GeosRow{}, g, tokens, hidden, stream, [](auto geo) { return rms_norm_v2_kernel<geo.RT, geo.RV, Src>; },
+                              (half_t*)out_f16, src, (const half_t*)weight_f16, eps, hidden, nv);
+  });
 }
 
 // Fused extension: kv4_decode_merge_kernel + omni_quant_fuse_sum in one kernel (one workgroup per token).
@@ -952,20 +905,13 @@ extern "C" int omni_attn_merge_quant_fuse_sum(void* out_i8, const void* part_ml_
   const int nv = norm_block(hidden, false);
   if (!v2_ok(hidden, nv)) return OMNI_EINVAL;
   if (batch == 0) return OMNI_OK;
-  SrcAttnMerge src{(const float*)part_ml_f32, (const float*)part_o_f32, nsplit, num_heads, 0};
-  const bool v2_batched = false;
-  if (sum_f16) {
-    #undef KQ_
-    #define KQ_(RT_, RV_) quant_v2_kernel<RT_, RV_, true, SrcAttnMerge>
-    OMNI_V2_LAUNCH(KQ_, batch, hidden, hidden, (int8_t*)out_i8, src, (half_t*)sum_f16,
-                   (half_t*)scale_f16, hidden, nv);
-  } else {
-    #undef KQ_
-    #define KQ_(RT_, RV_) quant_v2_kernel<RT_, RV_, false, SrcAttnMerge>
-    OMNI_V2_LAUNCH(KQ_, batch, hidden, hidden, (int8_t*)out_i8, src, (half_t*)nullptr,
-                   (half_t*)scale_f16, hidden, nv);
-  }
-  return omni_launch_status();
+  const SrcAttnMerge src{(const float*)part_ml_f32, (const float*)part_o_f32, nsplit, num_heads, 0};
+  const RowGeom g = row_geometry(ROWS_QUANT_NORM, batch, hidden, nv, SrcAttnMerge::BATCH);
+  return with_flag(sum_f16, [&](auto fuse) {
+    constexpr bool FS = decltype(fuse)::value;
+    return launch_rows<true>(GeosRow{}, g, batch, hidden, stream, [](auto geo) { return quant_v2_kernel<geo.RT, geo.RV, FS, SrcAttnMerge>; },
+                             (int8_t*)out_i8, src, (half_t*)sum_f16, (half_t*)scale_f16, hidden, nv);
+  });
 }
 
 // Fused extension (row-kernel-free decode layer): the flash-decoding merge alone, as a WIDE kernel -- one thread per 8
@@ -1052,23 +998,12 @@ extern "C" int omni_tp_add_rms_norm_general_fuse_sum(void* out_i8, void* residua
   // this row kernel carries no L2-prefetch riders (its workgroups meet at a ticket and must all be resident): a descriptor
   // armed for "the next row kernel" is dropped here instead of riding on an unrelated launch later
   (void)take_armed_prefetch();
-  const size_t lds = (size_t)hidden * sizeof(float);
-  // vectors per thread = what the row needs (the source batches its requests: an unused vector would re-read element 0 of
-  // every peer): 1 up to 4096 columns, 2 up to 8192 (Llama-2-70B), 4 beyond
-#define OMNI_TP_NORM(RV_)                                                                                                         \
-  do {                                                                                                                            \
-    if (sum_f16)                                                                                                                  \
-      hipLaunchKernelGGL((tp_add_norm_v2_kernel<512, RV_, true>), dim3(tokens), dim3(512), lds, (hipStream_t)stream,              \
-                         (int8_t*)out_i8, src, (const half_t*)weight_f16, (half_t*)sum_f16, (half_t*)scale_f16, eps, hidden, nv); \
-    else                                                                                                                          \
-      hipLaunchKernelGGL((tp_add_norm_v2_kernel<512, RV_, false>), dim3(tokens), dim3(512), lds, (hipStream_t)stream,             \
-                         (int8_t*)out_i8, src, (const half_t*)weight_f16, (half_t*)nullptr, (half_t*)scale_f16, eps, hidden, nv); \
-  } while (0)
-  if (hidden <= 512 * VT) OMNI_TP_NORM(1);
-  else if (hidden <= 512 * 2 * VT) OMNI_TP_NORM(2);
-  else OMNI_TP_NORM(4);
-#undef OMNI_TP_NORM
-  return omni_launch_status();
+  const RowGeom g = row_geometry(ROWS_TP_NORM, tokens, hidden, nv, SrcPeerAdd::BATCH);
+  return with_flag(sum_f16, [&](auto fuse) {
+    constexpr bool FS = decltype(fuse)::value;
+    return launch_rows<false>(GeosTp{}, g, tokens, hidden, stream, [](auto geo) { return tp_add_norm_v2_kernel<geo.RT, geo.RV, FS>; },
+                              (int8_t*)out_i8, src, (const half_t*)weight_f16, (half_t*)sum_f16, (half_t*)scale_f16, eps, hidden, nv);
+  });
 }
 
 // ------------------------------------------------------------------------------------------

@@ -1,4 +1,19 @@
-"""Parity of quant / norm / activation kernels against the oracle."""
+"""Parity of quant / norm / activation kernels against the oracle.
+
+Which case reaches which branch of the row-kernel dispatch (row_geometry() in csrc/elementwise.hip):
+  <512, 4> decode rows               (16 | 3) x 4096, 3 x 16384 of test_quant / test_rms_norm_general / test_rms_norm / the add form
+  <128, 4> many short rows           1024 x 512, 1100 x 4096
+  <256, 8> many rows                 1024 x 12288, 1030 x 14336 / 8192  (covers every many-row launch up to 16384 columns: no
+                                     many-row launch reaches <512, 4>; 1024 x 16416 is longer than every v2 geometry)
+  first generation by divisibility   3 x 100 (rms_norm_general[_fuse_sum], the add form)
+  first generation by length         2 x 32800, 1024 x 16416 (quant[_fuse_sum]); 3 x 32800, 2 x 16416 (SiLU)
+  SiLU <512, 8> / first generation   3 x 28672 / 1024 x 28672, with and without the row sum
+  slab consumers                     test_deferred_splitk_*: per channel 16 x 8192 (<512, 2>, batched source), 16 x 4096; W8A8 /
+                                     per group with and without the row sum; the final norm with and without zero terms
+  merge + quant                      bit for bit through the runner tests: with the row sum DecodeRunner's fused levels against
+                                     the reference sequence (tests/test_runtime_gpu.py), without it the LServe runner at
+                                     fused = 2 against its eager sequence (tests/test_lserve_runtime_gpu.py)
+  tensor-parallel norm               tests/test_tp_gpu.py: 4096 / 8192 / 12288 columns = <512, 1 | 2 | 4>"""
 import numpy as np
 import pytest
 import torch
@@ -15,7 +30,9 @@ def _x(tokens, hidden, seed, scale=1.0):
 
 
 @pytest.mark.parametrize("tokens,hidden", [(1, 128), (16, 4096), (37, 14336), (5, 1024), (3, 28672), (0, 4096),
-                                           (1100, 4096), (1030, 14336)])   # many rows: 128 / 256 threads per row
+                                           (1100, 4096), (1030, 14336),    # many rows: 128 / 256 threads per row
+                                           (3, 16384), (1024, 512), (1024, 12288),         # the row-count threshold itself
+                                           (1024, 16416), (2, 32800)])     # longer than every v2 geometry: first generation
 @pytest.mark.parametrize("fuse", [False, True])
 def test_quant(tokens, hidden, fuse):
     import omniserve_backend.fused_kernels as fk
@@ -37,7 +54,9 @@ def test_quant(tokens, hidden, fuse):
         assert_f16_equal(ssum, sm, "sum")
 
 
-@pytest.mark.parametrize("tokens,hidden", [(1, 128), (16, 4096), (33, 8192), (7, 5120), (4, 96), (1100, 4096), (1030, 8192)])
+@pytest.mark.parametrize("tokens,hidden", [(1, 128), (16, 4096), (33, 8192), (7, 5120), (4, 96), (1100, 4096), (1030, 8192),
+                                           (3, 16384), (1024, 512), (1024, 12288),
+                                           (3, 100)])      # not a multiple of 8: first generation
 @pytest.mark.parametrize("fuse", [False, True])
 def test_rms_norm_general(tokens, hidden, fuse):
     import omniserve_backend.layernorm_ops as ln
@@ -58,7 +77,7 @@ def test_rms_norm_general(tokens, hidden, fuse):
         assert_f16_equal(ssum, sm, "sum")
 
 
-@pytest.mark.parametrize("tokens,hidden", [(1, 128), (16, 4096), (9, 8192), (1100, 4096)])
+@pytest.mark.parametrize("tokens,hidden", [(1, 128), (16, 4096), (9, 8192), (1100, 4096), (3, 16384), (1024, 512), (1024, 12288)])
 def test_rms_norm(tokens, hidden):
     import omniserve_backend.layernorm_ops as ln
     x = _x(tokens, hidden, tokens, 2.0)
@@ -83,7 +102,8 @@ def test_silu_and_mul(tokens, d):
     assert (np.asarray(out.cpu().numpy()).view(np.uint16) != want.view(np.uint16)).mean() < 1e-3
 
 
-@pytest.mark.parametrize("tokens,hidden", [(16, 4096), (5, 8192), (3, 128), (1100, 4096)])
+@pytest.mark.parametrize("tokens,hidden", [(16, 4096), (5, 8192), (3, 128), (1100, 4096), (3, 16384), (1024, 512),
+                                           (1024, 12288), (3, 100)])       # (3, 100): first generation
 def test_fused_add_norm_matches_the_two_reference_calls(tokens, hidden):
     import omniserve_backend.layernorm_ops as ln
     from omniserve_amd.backend import fused_ext
@@ -105,10 +125,11 @@ def test_fused_add_norm_matches_the_two_reference_calls(tokens, hidden):
 
 
 @pytest.mark.parametrize("tokens,d", [(16, 14336), (3, 28672), (5, 128), (1030, 14336), (128, 28672), (5, 32768), (2, 16416),
-                                      (3, 32800)])
+                                      (3, 32800), (1024, 28672)])
 def test_fused_silu_mul_quant_matches_the_two_kernels(tokens, d):
     """Compared against the HIP silu_and_mul + quant pair (both go through the same device expf).  Rows of 16384 < d <= 32768
-    (Llama-2-70B's 28672) take the <512, 8> geometry with 112 - 128 KiB of LDS, wider ones the one-kernel-per-row fallback."""
+    (Llama-2-70B's 28672) take the <512, 8> geometry with 112 - 128 KiB of LDS, wider ones -- and 1024 rows or more of these --
+    the one-kernel-per-row fallback."""
     import omniserve_backend.activation_ops as act
     import omniserve_backend.fused_kernels as fk
     from omniserve_amd.backend import fused_ext
@@ -121,6 +142,23 @@ def test_fused_silu_mul_quant_matches_the_two_kernels(tokens, d):
     fused_ext.silu_mul_quant_fuse_sum(q2, x, m2, s2)
     torch.cuda.synchronize()
     assert torch.equal(q1, q2) and torch.equal(s1.view(torch.int16), s2.view(torch.int16)) and torch.equal(m1.view(torch.int16), m2.view(torch.int16))
+
+
+@pytest.mark.parametrize("tokens,d", [(16, 14336), (3, 28672), (1024, 28672), (1024, 4096)])
+def test_fused_silu_mul_quant_without_the_row_sum(tokens, d):
+    """sum = None against the HIP silu_and_mul + invoke_quant pair, over the same geometries as the summing form."""
+    import omniserve_backend.activation_ops as act
+    import omniserve_backend.fused_kernels as fk
+    from omniserve_amd.backend import fused_ext
+    x = to_dev(_x(tokens, 2 * d, tokens + d, 2.0))
+    tmp = torch.empty((tokens, d), dtype=torch.float16, device=dev())
+    act.silu_and_mul(tmp, x)
+    q1 = torch.empty((tokens, d), dtype=torch.int8, device=dev()); s1 = torch.empty((tokens,), dtype=torch.float16, device=dev())
+    fk.invoke_quant(q1, tmp, s1)
+    q2 = torch.empty_like(q1); s2 = torch.empty_like(s1)
+    fused_ext.silu_mul_quant_fuse_sum(q2, x, None, s2)
+    torch.cuda.synchronize()
+    assert torch.equal(q1, q2) and torch.equal(s1.view(torch.int16), s2.view(torch.int16))
 
 
 @pytest.mark.parametrize("M,N,K", [(16, 4096, 4096), (16, 8192, 1024), (7, 5120, 2048)])
@@ -201,6 +239,39 @@ def test_deferred_splitk_w8_epilogue_matches_gemm_then_add_norm(M, N, K):
     assert np.array_equal(q2.cpu().numpy(), qo)
     assert_f16_equal(sc2, so, "scale")
     assert_f16_equal(sm2, smo, "sum")
+
+
+def test_deferred_splitk_w8_epilogue_without_the_row_sum():
+    """sum = None (the W8A8 / per-group layers read none): residual, codes and scales of the summing form, nothing else written."""
+    from omniserve_amd.backend import fused_ext
+    M, N, K = 3, 2048, 4096
+    rng = np.random.default_rng(M + K)
+    w = rng.integers(-128, 128, size=(N, K), dtype=np.int8)
+    sw = rng.uniform(0.0002, 0.0014, size=(N,)).astype(np.float16)
+    a, sa, _ = oe.quant_per_token(_x(M, K, 5, 1.0), False)
+    resid = _x(M, N, 6, 2.0)
+    g = (1.0 + 0.1 * rng.standard_normal(N)).astype(np.float16)
+    w_d, sw_d, a_d, sa_d, g_d = map(to_dev, (w, sw, a, sa, g))
+    slab = torch.empty((64 << 20,), dtype=torch.uint8, device=dev())
+    sk = fused_ext.gemm_partial_w8a8(a_d, w_d, slab)
+    outs = []
+    for with_sum in (True, False):
+        x = to_dev(resid)
+        q = torch.empty((M, N), dtype=torch.int8, device=dev())
+        sc = torch.empty((M,), dtype=torch.float16, device=dev())
+        sm = torch.full((M,), 7.0, dtype=torch.float16, device=dev())
+        fused_ext.splitk_w8_add_rms_norm_general_fuse_sum(q, x, slab, sk, sw_d, sa_d, g_d, sm if with_sum else None, sc, 1e-5)
+        torch.cuda.synchronize()
+        outs.append((x.cpu().numpy(), q.cpu().numpy(), sc.cpu().numpy()))
+        assert with_sum or (sm == 7.0).all()
+    for u, v in zip(*outs):
+        assert np.array_equal(u.view(np.uint8), v.view(np.uint8))
+    from oracle import w4a8
+    want = w4a8.gemm_w8a8(a, w, sw, sa)
+    xs = (resid.astype(np.float32) + want.astype(np.float32)).astype(np.float16)
+    qo, so, _ = oe.rms_norm_general(xs, g, 1e-5, False)
+    assert np.array_equal(outs[1][1], qo)
+    assert_f16_equal(outs[1][2], so, "scale")
 
 
 @pytest.mark.parametrize("M,N,K", [(16, 4096, 4096), (64, 4096, 14336), (5, 1024, 2048)])
